@@ -13,10 +13,19 @@ H=768 on 1/2/4/8 GPUs), so for N > 1 `value` is that problem with H/N heads per 
 contract's barrier + max over ranks); the object `weak` beside it holds the weak-scaled job of the same run (every rank runs
 the full per-GPU shape on its own 768 heads).  At N = 1 the two coincide.
 
-Output: the LAST stdout line is the contract line (< 4 KB: contract keys, `roofline`, `roofline_fwd`, `cpu_baseline`, kernel
-times and a [fwd, bwd] ms digest per table row).  The tables themselves -- BASELINE sweep (B=16, H=768, L = 1K .. 1M), gated
-sweep rows, configs[1..4], the reference's README table -- are printed before it, one JSON line per row, and the complete
-object goes to gpurun_out/bench_full.json.
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, preheat + W warm-up steps, K timed steps,
+the outputs of the last timed step if `--dump-outputs DIR` is given, and the contract line (contract keys, `ms_per_step`, the two
+TFLOP/s figures).
+
+`--full` adds everything else, after the headline: the recompute-mode step, the torch.utils.benchmark timing, per-kernel times and
+the roofline objects, the box's measured peaks, the CPU baseline, and (N = 1) the tables -- BASELINE sweep (B=16, H=768,
+L = 1K .. 1M), gated sweep rows, configs[1..4], the reference's README table -- or (N > 1) the weak-scaled job and the strong-scaled
+rows.  The tables are printed before the contract line, one JSON line per row; the line carries `roofline`, `roofline_fwd`,
+`cpu_baseline`, kernel times and a [fwd, bwd] ms digest per table row; the complete object goes to bench_out/bench_full.json.
+
+`--dump-outputs DIR`: what a caller of the timed step receives from its last step, as float32 .npy files -- y = the forward output,
+du = u.grad, dk = k.grad -- each a fixed, seeded sample of DUMP_ROWS rows (full rows of L), about 50 MB in all.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse, hashlib, json, os, sys, time
 
@@ -222,6 +231,19 @@ def cpu_baseline(seconds_per_point=3.0):
 
 
 PREHEAT_S = 0.5
+DUMP_ROWS = 256
+
+
+def dump_outputs(d, y, du, dk):
+    """y, du: (B, H, L); dk: (H, L) -> d/{y,du,dk}.npy in float32, DUMP_ROWS rows of each picked by a fixed seed"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    rng = np.random.default_rng(0)
+    for name, t in (("y", y), ("du", du), ("dk", dk)):
+        t = t.detach().reshape(-1, t.shape[-1])
+        rows = np.sort(rng.choice(t.shape[0], size=min(DUMP_ROWS, t.shape[0]), replace=False))
+        a = t[torch.from_numpy(rows).to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 def timed_steps(step, steps, warmup, dist, dev):
@@ -287,8 +309,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sweep", action="store_true")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline step (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-sweep", action="store_true", help="--full without the tables")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -316,10 +340,16 @@ def main():
     k = torch.randn(H, L, device=dev).requires_grad_(True)
     dout = torch.randn(B, H, L, device=dev).to(dtype)
     mod = FlashFFTConv(N, dtype=dtype).to(dev)
+    # --dump-outputs: the forward output of the last step is kept (detached: no reference to the autograd graph)
+    keep_y = args.dump_outputs is not None and rank == 0
+    last = {}
 
     def step():
         u.grad = None; k.grad = None
-        mod(u, k).backward(dout)
+        y = mod(u, k)
+        y.backward(dout)
+        if keep_y:
+            last["y"] = y.detach()
 
     # Preheat (untimed, before the W warm-up steps): a fresh process starts with the GPU in a low power state and the first
     # ~100 steps run 3-6 % slower than steady state (measured: W=5 1.35 ms, W=50 1.29, W=300 1.27 per step at K=20), so the
@@ -331,7 +361,67 @@ def main():
             step()
         torch.cuda.synchronize()
         preheat += 10
-    el = timed_steps(step, args.steps, args.warmup, dist, dev)
+
+    # ---- the headline.  N = 1: the step above.  N > 1: strong scaling, the FIXED B=16 x H=768 problem, this rank's H/world heads
+    # (no collective in the data path)
+    strong = None
+    if world == 1:
+        el = timed_steps(step, args.steps, args.warmup, dist, dev)
+        outs = (u.grad, k.grad)
+    else:
+        s0, s1 = head_range(H, rank, world)
+        us = u.detach()[:, s0:s1].contiguous().requires_grad_(True)
+        ks = k.detach()[s0:s1].contiguous().requires_grad_(True)
+        ds = dout[:, s0:s1].contiguous()
+
+        def step_s():
+            us.grad = None; ks.grad = None
+            y = mod(us, ks)
+            y.backward(ds)
+            if keep_y:
+                last["y"] = y.detach()
+        el_s = timed_steps(step_s, args.steps, args.warmup, dist, dev)
+        outs = (us.grad, ks.grad)
+        strong = {"value": B * H / (el_s / args.steps), "unit": "seq/s", "ms_per_step": el_s / args.steps * 1e3,
+                  "scaling": "strong", "heads_per_rank": s1 - s0,
+                  "workload": f"the fixed B={B} H={H} L={L} problem, {H}//{world} heads per rank"}
+    if keep_y:
+        dump_outputs(args.dump_outputs, last.pop("y"), *outs)
+    del outs
+
+    rows = B * H
+    dense_fwd = flops_dense_fwd_per_row(N)
+    fft_fwd, fft_bwd = flops_fft_equiv(N)
+    head_value = strong["value"] if strong is not None else world * rows / (el / args.steps)
+    head_ms = strong["ms_per_step"] if strong is not None else el / args.steps * 1e3
+    out = {
+        "metric": "FFT-conv fwd+bwd seq/s, B=16 H=768 L=16384 fft=32768 bf16",
+        "value": head_value, "unit": "seq/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "preheat_steps": preheat,
+        "ms_per_step": head_ms, "higher_is_better": True,
+        "scaling": "weak" if world == 1 else "strong", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": "FlashFFTConv(32768) B=16 H=768 L=16384 bf16, fwd+bwd incl. k->k_f and dk (BASELINE configs[1])",
+                   "rows_per_step": rows, "heads_per_rank": (strong or {}).get("heads_per_rank", H),
+                   "parallelism": f"head-shard x{world} (no collective)"},
+        # TFLOP/s of the SAME step as `value` (N > 1: the fixed problem's rows over the strong-scaled step; ADVICE r05)
+        "tflops_dense_monarch": rows * dense_fwd * 2.5 / (head_ms * 1e-3) / 1e12,
+        "tflops_fft_equiv": rows * (fft_fwd + fft_bwd) / (head_ms * 1e-3) / 1e12,
+    }
+    if strong is not None:
+        out["strong"] = strong
+    # one place that says it: no multi-GPU run has ever been measured by the builder (every box has ONE GPU; RCCL has only run world-size-1)
+    out["scaling_note"] = "N>1 never measured by the builder: 1-GPU boxes only" if world == 1 else None
+    if not args.full:
+        if rank == 0:
+            emit(out)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full from here on
+    if world > 1:       # the weak-scaled job of the same run: every rank runs the full per-GPU shape on its own 768 heads
+        el = timed_steps(step, args.steps, args.warmup, dist, dev)
     # the same step with the reference's memory footprint (FFT(u) recomputed by the backward kernel)
     mod.save_spectrum = False
     el_rc = timed_steps(step, args.steps, args.warmup, dist, dev)
@@ -340,22 +430,6 @@ def main():
     # comparability with its published tables; the contract figure above is the barrier-bracketed wall clock
     from torch.utils import benchmark as tbench
     timer_ms = tbench.Timer(stmt="step()", globals={"step": step}).timeit(args.steps).mean * 1e3
-
-    # ---- strong scaling: the FIXED B=16 x H=768 problem, this rank's H/world heads (no collective in the data path)
-    strong = None
-    if world > 1:
-        s0, s1 = head_range(H, rank, world)
-        us = u.detach()[:, s0:s1].contiguous().requires_grad_(True)
-        ks = k.detach()[s0:s1].contiguous().requires_grad_(True)
-        ds = dout[:, s0:s1].contiguous()
-
-        def step_s():
-            us.grad = None; ks.grad = None
-            mod(us, ks).backward(ds)
-        el_s = timed_steps(step_s, args.steps, args.warmup, dist, dev)
-        strong = {"value": B * H / (el_s / args.steps), "unit": "seq/s", "ms_per_step": el_s / args.steps * 1e3,
-                  "scaling": "strong", "heads_per_rank": s1 - s0,
-                  "workload": f"the fixed B={B} H={H} L={L} problem, {H}//{world} heads per rank"}
 
     strong_rows = None
     if world > 1 and not args.no_sweep:
@@ -430,12 +504,9 @@ def main():
             dist.destroy_process_group()
         return
 
-    rows = B * H
     npair = (B // 2) * H
     sec_per_step = el / args.steps
     seq_s = world * rows / sec_per_step
-    dense_fwd = flops_dense_fwd_per_row(N)
-    fft_fwd, fft_bwd = flops_fft_equiv(N)
     # Roofline objects: `roofline` = the dominant kernel of the step (the fused backward, ~60 % of the step time),
     # `roofline_fwd` = the forward conv_kernel.  Three yardsticks, all per launch and all over the launch time measured
     # above with HIP events:
@@ -502,25 +573,8 @@ def main():
         r["frac_traffic"] = r["traffic"] / (r["launch_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS if r["traffic"] else None
     roof_bwd_rc = roof("bwd_kernel<Geo<32,32,32>,bf16,HALF> recomputing FFT(u) (save_spectrum = False)", mf_bwd, dense_bwd, bwd_bytes,
                        kt["bwd_fused"], prof_traffic("r02_pmc_bwd_kernel.txt", "traffic"))
-    # N > 1: the contract value is the FIXED problem (strong), the weak-scaled job rides beside it
-    weak = None
-    if strong is not None:
-        weak = {"value": seq_s, "unit": "seq/s", "ms_per_step": sec_per_step * 1e3, "scaling": "weak", "heads_per_rank": H}
-    head_value = strong["value"] if strong is not None else seq_s
-    head_ms = strong["ms_per_step"] if strong is not None else sec_per_step * 1e3
-    out = {
-        "metric": "FFT-conv fwd+bwd seq/s, B=16 H=768 L=16384 fft=32768 bf16",
-        "value": head_value, "unit": "seq/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "preheat_steps": preheat,
-        "ms_per_step": head_ms, "ms_per_step_torch_benchmark_timer": timer_ms, "higher_is_better": True,
-        "scaling": "weak" if world == 1 else "strong", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": "FlashFFTConv(32768) B=16 H=768 L=16384 bf16, fwd+bwd incl. k->k_f and dk (BASELINE configs[1])",
-                   "rows_per_step": rows, "heads_per_rank": (strong or {}).get("heads_per_rank", H),
-                   "parallelism": f"head-shard x{world} (no collective)"},
-        # TFLOP/s of the SAME step as `value` (N > 1: the fixed problem's rows over the strong-scaled step; ADVICE r05)
-        "tflops_dense_monarch": rows * dense_fwd * 2.5 / (head_ms * 1e-3) / 1e12,
-        "tflops_fft_equiv": rows * (fft_fwd + fft_bwd) / (head_ms * 1e-3) / 1e12,
+    out.update({
+        "ms_per_step_torch_benchmark_timer": timer_ms,
         "kernel_ms": {n: v * 1e3 for n, v in kt_step.items()},
         "kernel_ms_how": "HIP events between the launches of 20 back-to-back steps: conv_fwd_k + conv_bwd_k = the module's two launches "
                          "(round 4); kfft / conv_fwd_save / bwd_fused_saved / dk_ifft = the same work as round 3's four launches",
@@ -536,14 +590,13 @@ def main():
                               "no spectra kept between forward and backward)"},
         "saved_for_backward_bytes": {"u": B * H * L * 2, "k_f": H * N * 4, "spectra (save_spectrum)": npair * N * 4},
         "peak_measured": peaks,
-    }
+    })
     if strong is not None:
-        out["strong"], out["weak"] = strong, weak
+        # N > 1: the contract value is the FIXED problem (strong), the weak-scaled job rides beside it
+        out["weak"] = {"value": seq_s, "unit": "seq/s", "ms_per_step": sec_per_step * 1e3, "scaling": "weak", "heads_per_rank": H}
         out["kernel_ms_scaling"] = "weak"      # kernel_ms / roofline objects below time the full per-GPU shape (768 heads on this rank)
     if strong_rows:
         out["strong_rows"] = strong_rows
-    # one place that says it: no multi-GPU run has ever been measured by the builder (every box has ONE GPU; RCCL has only run world-size-1)
-    out["scaling_note"] = "N>1 never measured by the builder: 1-GPU boxes only" if world == 1 else None
     if world == 1 and not args.no_sweep:
         # the rest of the BASELINE metric, timed in this same process with HIP events (benchmarks/sweep.py): the other
         # configs and the L = 1K .. 1M sweep at B=16 H=768 (fwd / bwd ms at module level, incl. k -> k_f and dk)
@@ -561,7 +614,7 @@ def main():
         out["readme_table"] = list(SW.readme_rows())
     if world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
-    emit(out, os.path.join(ROOT, "gpurun_out", "bench_full.json"))
+    emit(out, os.path.join(ROOT, "bench_out", "bench_full.json"))
     if dist is not None:
         dist.destroy_process_group()
 

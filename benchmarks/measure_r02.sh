@@ -4,9 +4,9 @@
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r02_end; mkdir -p $O
 cd $R
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-sweep > $O/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o b -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-sweep > $O/stats.log 2>&1
 pmc() { drv=$1; name=$2; shift 2; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $O/$name -o p -- python $R/benchmarks/$drv > $O/$name.log 2>&1; }
 pmc prof_conv.py c1 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES
 pmc prof_conv.py c2 SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU

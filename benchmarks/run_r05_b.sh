@@ -29,4 +29,4 @@ for v in kf_late product; do
 done
 unset FFC_LIB
 cut -c1-400 $O/ab_multipass.txt
-python bench.py > $O/bench.txt 2> $O/bench.err; tail -c 2800 $O/bench.txt; cp gpurun_out/bench_full.json $O/ 2>/dev/null
+python bench.py --full > $O/bench.txt 2> $O/bench.err; tail -c 2800 $O/bench.txt; cp bench_out/bench_full.json $O/ 2>/dev/null

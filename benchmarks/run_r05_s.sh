@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r05_end; mkdir -p $O
 cd $R
-timeout 150 python bench.py > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json; cp gpurun_out/bench_full.json $O/bench_full.json
+timeout 150 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 300 $O/bench.json; cp bench_out/bench_full.json $O/bench_full.json
 cd /tmp
 timeout 60 rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg4_s -o s -- python $R/benchmarks/prof_one.py 4194304 1 16 1048576 both > $O/cfg4.log 2>&1
 timeout 60 rocprofv3 --kernel-trace --stats --output-format csv -d $O/cfg3_s -o s -- python $R/benchmarks/prof_one.py 16384 8 1024 8192 both gated > $O/cfg3.log 2>&1

@@ -19,4 +19,4 @@ for l in sys.stdin:
 done
 unset FFC_SAVE_SPECTRUM
 cat $O/ab_save_big.txt
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; cp gpurun_out/bench_full.json $O/bench_full.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; cp bench_out/bench_full.json $O/bench_full.json

@@ -89,3 +89,23 @@ def test_rows_that_ran_a_fitted_fft_size_are_flagged_on_the_line(tmp_path):
     assert len(last) < bench.LINE_LIMIT
     assert d["configs_fft_run"] == {"cfg4": 2097152} and d["configs_seqlen_points_fwd_bwd_ms"] == {"cfg4": [0.6864, 0.7577]}
     assert d["configs_fwd_bwd_ms"]["cfg4"][0] < 0.6
+
+
+def test_dump_outputs_are_float32_seeded_and_within_budget(tmp_path):
+    """--dump-outputs: y / du / dk as float32 .npy, the same seeded rows on every call, and at the headline shapes (B16 x H768 x
+    L16384) no more than 64 MB in all"""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(0)
+    y = torch.randn(4, 300, 64, generator=g).to(torch.bfloat16)
+    du = torch.randn(4, 300, 64, generator=g).to(torch.bfloat16)
+    dk = torch.randn(300, 64, generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), y, du, dk)
+    bench.dump_outputs(str(tmp_path / "b"), y, du, dk)
+    for name, t in (("y", y), ("du", du), ("dk", dk)):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (bench.DUMP_ROWS, 64)
+        assert np.array_equal(a, np.load(tmp_path / "b" / f"{name}.npy"))
+        rows = t.float().reshape(-1, 64).numpy()
+        assert all((rows == r).all(axis=1).any() for r in a)        # every dumped row is a row of the output, bit for bit
+    assert 3 * bench.DUMP_ROWS * bench.CFG["L"] * 4 <= 64e6

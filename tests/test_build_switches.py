@@ -4,7 +4,6 @@ inside every load).  One simulator build with every switch flipped, compared wit
 default simulator on forward, backward and the spectrum-saving pair of single-tile, fused and multi-pass sizes, gated and ragged."""
 import ctypes, hashlib, os, subprocess, sys
 import numpy as np
-import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 PKG = os.path.join(os.path.dirname(HERE), "flash-fft-conv_amd")
@@ -16,17 +15,21 @@ PKG = os.path.join(os.path.dirname(HERE), "flash-fft-conv_amd")
 ALT_FLAGS = ["-DFFC_GATE_BATCH=0", "-DFFC_RP_HOIST=0", "-DFFC_OUTER_QUAD=0", "-DFFC_RP_FASTK=0", "-DFFC_PK_GATE=0", "-DFFC_IP_MERGE=0"]
 
 
-def _alt_sim():
-    """built in-tree under lib/variants/sim_alt/ and reused while no source is newer"""
-    d = os.path.join(PKG, "lib", "variants", "sim_alt")
-    so = os.path.join(d, "libffcsim.so")
+def _variant_sim(name, flags, so_name="libffcsim.so"):
+    """a simulator built with `flags`, in-tree under lib/variants/<name>/ and reused while no source is newer"""
+    d = os.path.join(PKG, "lib", "variants", name)
+    so = os.path.join(d, so_name)
     csrc = os.path.join(PKG, "csrc")
     newest = max(os.path.getmtime(os.path.join(csrc, f)) for f in os.listdir(csrc))
     if not os.path.exists(so) or os.path.getmtime(so) < newest:
         os.makedirs(d, exist_ok=True)
-        subprocess.check_call(["g++", "-O0", "-std=c++17", "-fPIC", "-shared", "-pthread"] + ALT_FLAGS + ["-o", so,
+        subprocess.check_call(["g++", "-O0", "-std=c++17", "-fPIC", "-shared", "-pthread"] + list(flags) + ["-o", so,
                                os.path.join(csrc, "ffc_sim.cpp"), os.path.join(csrc, "ffc_plan.cpp")])
     return so
+
+
+def _alt_sim():
+    return _variant_sim("sim_alt", ALT_FLAGS)
 
 
 CASES = [(256, 200, 5, 2, 1, True), (1024, 1024, 3, 2, 0, True), (2048, 1024, 4, 1, 0, True), (2048, 1000, 3, 2, 1, False), (2048, 2048, 2, 1, 0, True), (4096, 2048, 5, 1, 1, True),
@@ -97,12 +100,9 @@ for (N, L, B, H, gated, dt) in [(32768, 16384, 3, 1, False, 0), (32768, 32768, 2
 
 def test_folded_outer_twiddle_variant_matches_the_oracle():
     """-DFFC_FOLD_TW=2: the outer twiddle folded into per-tile inner DFT matrices also at fft 32768 (forward kernels + the saved-spectra backward;
-    the product folds the forward of fft 16384 only).  The variant simulator takes ~6 min to compile, so this runs only where it has been built
-    (g++ -O0 -std=c++17 -fPIC -shared -pthread -DFFC_FOLD_TW=2 -o lib/variants/sim_fold/libffcsim2.so csrc/ffc_sim.cpp csrc/ffc_plan.cpp)."""
-    so = os.path.join(PKG, "lib", "variants", "sim_fold", "libffcsim2.so")
-    csrc = os.path.join(PKG, "csrc")
-    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(os.path.join(csrc, f)) for f in ("ffc_body.h", "ffc_modes.h", "ffc_plan.cpp")):
-        pytest.skip("variant simulator not built (or older than the kernel sources)")
+    the product folds the forward of fft 16384 only).  The variant simulator is built on first use (a few minutes of g++ -O0) under
+    lib/variants/sim_fold/ and reused while no source is newer."""
+    so = _variant_sim("sim_fold", ["-DFFC_FOLD_TW=2"], "libffcsim2.so")
     env = dict(os.environ, FFC_SIM_LIB=so)
     r = subprocess.run([sys.executable, "-c", _FOLD_SCRIPT % (HERE, PKG, os.path.dirname(HERE))], env=env, capture_output=True, text=True, timeout=1800)
     assert r.returncode == 0, r.stderr[-2000:]
