@@ -197,11 +197,53 @@ class SimOps:
         assert self.nslab > 0
         return ws
 
+    def bwd(self, dt, M, xd, xu, kf, z=None):
+        """fused inner backward on pair-plane rows: (input gradient rows, fp32 dk_f slabs), as _TorchOps.bwd"""
+        assert z is None
+        Bp, hp, _ = xd.shape
+        nt, _, _, _ = plan_info(M, dt)
+        ws = np.full(lib().ffcsim_upw(M) * hp * nt * 2048, np.nan, np.float32)
+        yd = np.zeros_like(xd)
+        self.nslab = lib().ffcsim_conv_bwd(M, dt, p(xd), p(xu), p(kf), None, None, p(yd), None, None, p(ws), Bp, hp, M, 1)
+        assert self.nslab > 0
+        return yd, ws
+
     def dkifft_c(self, M, ws, Bp, hp, scale):
         out = np.zeros((2, hp, M), np.uint16)
         rc = lib().ffcsim_kernel_ifft_grad_c(M, p(ws), self.nslab, hp, p(out), ctypes.c_float(scale))
         assert rc == 0, rc
         return out
+
+    # the fused inner calls of the product (_TorchOps.conv_kx / bwd_dk: ffc_conv_fwd_kx / ffc_conv_bwd_kx), inner sizes 8192 .. 32768 -- the
+    # sizes whose convolution launch transforms its own k_f rows and whose backward launch inverts its own dk_f sums
+    def conv_kx(self, dt, M, x, xk, scale, keep=False):
+        """k_f rows from their complex input xk inside the convolution launch -> (y, k_f, None): the simulator keeps no spectra here"""
+        assert 8192 <= M <= 32768 and not keep
+        Bp, hp, _ = x.shape
+        nt, _, _, _ = plan_info(M, dt)
+        kf = np.full((hp, nt * 1024, 2), 0x7fc0 if dt == DT_BF16 else 0x7e00, np.uint16)      # NaN: the launch writes every k_f tile it reads
+        lib().ffcsim_set_fused_kx(p(xk), ctypes.c_float(scale))
+        try:
+            y = sim_conv_fwd(M, dt, x, kf)
+        finally:
+            lib().ffcsim_set_fused_kx(None, ctypes.c_float(1.0))
+        return y, kf, None
+
+    def bwd_dk(self, dt, M, xd, xu, kf, z, scale):
+        """input-gradient rows + the dk rows as a complex pair-plane tensor (bf16) out of ONE backward launch: no fp32 slab is written"""
+        assert 8192 <= M <= 32768 and z is None
+        Bp, hp, _ = xd.shape
+        nt, _, _, _ = plan_info(M, dt)
+        ws = np.full(lib().ffcsim_upw(M) * hp * nt * 2048, np.nan, np.float32)
+        yd = np.zeros_like(xd)
+        out = np.full((2, hp, M), 0x7fc0, np.uint16)
+        lib().ffcsim_set_fused_dkpair(p(out), ctypes.c_float(scale))
+        try:
+            assert lib().ffcsim_conv_bwd(M, dt, p(xd), p(xu), p(kf), None, None, p(yd), None, None, p(ws), Bp, hp, M, 1) > 0
+        finally:
+            lib().ffcsim_set_fused_dkpair(None, ctypes.c_float(1.0))
+        assert np.isnan(ws).all(), "the fused dk tail must not write slabs"
+        return yd, out
 
 
 def sim_bwd(N, dtype, dout_bits, u_bits, kf_bits, Lk, pre=None, post=None, nchunk=1, fused_dk=False):
@@ -265,3 +307,22 @@ def sim_fwd_bwd_z(N, dtype, u_bits, dout_bits, kf_bits, pre=None, post=None, nch
     finally:
         lib().ffcsim_set_z(None, None, 0)
     return y, du, dpre, dpost, ws[: nslab * H * nt * 2048].copy()
+
+
+def big_forward_and_dk(ops, dt, N, fac, ub, db, k, pre=None, post=None):
+    """One call of an HBM-level size on the simulator through flashfftconv.bigfft, the way conv._big_forward runs it: k -> inner k_f rows, the levels over
+    u (* pregate), the inner convolution, the inverse level (* postgate); and the UNGATED dk of (dout, u) through the dk_f kernel and its levels.
+    ub, db, pre, post: (B, H, L) bit tensors, k (H, L) fp32.  Returns a dict: out (bits), dk (fp32), and kf, x, y (the inner k_f rows, input rows,
+    output rows) and xd (the levels over dout) for callers that go on to the gradients."""
+    from flashfftconv import bigfft as BG
+    B, H, L = ub.shape
+    M = fac[1]
+    kf = BG.kernel_fft(ops, dt, N, k, H, L, fac)
+    x = BG.levels_forward(ops, dt, N, ub, B, H, L, pre, fac)
+    y = ops.conv(dt, M, x, kf, False)
+    out = np.zeros_like(ub)
+    BG.levels_inverse(ops, dt, N, y, out, B, H, L, post, None, fac)
+    xd = BG.levels_forward(ops, dt, N, db, B, H, L, None, fac)
+    xu = x if pre is None else BG.levels_forward(ops, dt, N, ub, B, H, L, None, fac)
+    dk = BG.dk_from_slabs(ops, N, ops.dkf(dt, M, xd, xu), xu.shape[0], H, L, None, fac)
+    return {"out": out, "dk": dk, "kf": kf, "x": x, "y": y, "xd": xd}

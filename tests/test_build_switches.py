@@ -111,3 +111,70 @@ def test_folded_outer_twiddle_variant_matches_the_oracle():
     for y, du, dk, dt in rows:
         tol = 1.2e-2 if dt == "0" else 1.5e-3
         assert float(y) < tol and float(du) < tol and float(dk) < 1.8e-2, (y, du, dk, dt)
+
+
+# ---------------------------------------------------------------- FFC_BIG_CHAIN=0 (csrc/ffc_big.h): the HBM levels with one sin / cos pair per element
+# instead of the twiddle chains down the rows -- the documented A/B build of round 5.  Another rounding sequence of the same values, so no bit identity:
+# the oracle's gate, and the default simulator to rounding.
+NOCHAIN_CASES = [(65536, ((16,), 4096), 30000, False, True), (131072, ((32,), 4096), 131072, True, True),
+                 (262144, ((64,), 4096), 131072, False, True), (262144, ((64,), 4096), 131072, False, False),
+                 (524288, ((128,), 4096), 100004, True, True), (524288, ((128,), 4096), 100004, True, False)]      # N, fac, L, gated, one_launch
+_NOCHAIN_SCRIPT = r'''
+import sys, numpy as np
+sys.path[:0] = [%r, %r, %r]
+import simlib as S
+res = {}
+for ci, (N, fac, L, gated, one_launch) in enumerate(%r):
+    for B in (1, 2):          # a batch of one: the half-row form (BigArgs::half); two rows: the pair form, all rows
+        rng = np.random.default_rng(N + L + B)
+        dt, H = 0, 2
+        ops = S.SimOps(); ops.half = B == 1; ops.one_launch = one_launch
+        u, g1, g2, d = (rng.standard_normal((B, H, L)).astype(np.float32) for _ in range(4))
+        k = (rng.standard_normal((H, L)) * 0.05).astype(np.float32)
+        ub, g1b, g2b, db = (S.to_bits(x, dt) for x in (u, g1, g2, d))
+        r = S.big_forward_and_dk(ops, dt, N, fac, ub, db, k, g1b if gated else None, g2b if gated else None)      # (shared with tests/test_sim_kernels.py)
+        res["out_%%d_%%d" %% (ci, B)] = S.from_bits(r["out"], dt); res["dk_%%d_%%d" %% (ci, B)] = r["dk"]
+        res["in_%%d_%%d" %% (ci, B)] = np.stack([u, g1, g2, d]); res["k_%%d_%%d" %% (ci, B)] = k
+        print(ci, B, flush=True)
+np.savez(sys.argv[1], **res)
+'''
+
+
+def _nochain_runs(libs_and_paths):
+    """the child script once per (simulator library or None = the default build, result file), side by side"""
+    src = _NOCHAIN_SCRIPT % (HERE, PKG, os.path.dirname(HERE), NOCHAIN_CASES)
+    procs = []
+    for sim_lib, path in libs_and_paths:
+        env = dict(os.environ)
+        env.pop("FFC_SIM_LIB", None)
+        if sim_lib:
+            env["FFC_SIM_LIB"] = sim_lib
+        procs.append(subprocess.Popen([sys.executable, "-c", src, path], env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True))
+    for pr in procs:
+        _, err = pr.communicate(timeout=1800)
+        assert pr.returncode == 0, err[-2000:]
+    return [np.load(path) for _, path in libs_and_paths]
+
+
+def test_per_element_twiddle_variant_matches_the_oracle(tmp_path):
+    """-DFFC_BIG_CHAIN=0: the per-element twiddle branches of the inverse level (BigBody::stage<false>, the one-launch / per-pass inverse of the factors
+    64 and 128) have to weight the stored rows of the half-row form like the chained form does (half_weight: 2, or 1 for the rows k0 = 0 and K / 2) --
+    without it the mirror rows are dropped and forward and dk of every batch of one are wrong by ~0.7 with no error raised.  Forward and dk of the
+    simulator's levels, half rows (B = 1) and all rows (B = 2), against the float64 oracle and against the default build."""
+    from oracle import ref_fft_conv as O
+    import simlib as S
+    rel = lambda a, b: np.linalg.norm(np.asarray(a).astype(np.float64) - b) / max(np.linalg.norm(b), 1e-30)
+    q = lambda x: S.from_bits(S.to_bits(x, 0), 0).astype(np.float64)
+    alt, base = _nochain_runs([(_variant_sim("sim_nochain", ["-DFFC_BIG_CHAIN=0"]), str(tmp_path / "nochain.npz")), (None, str(tmp_path / "default.npz"))])
+    for ci, (N, fac, L, gated, one_launch) in enumerate(NOCHAIN_CASES):
+        for B in (1, 2):
+            u, g1, g2, d = base[f"in_{ci}_{B}"]
+            k = base[f"k_{ci}_{B}"]
+            ref = O.ref_fft_conv_gated(q(u), k, q(g1), q(g2), N, dtype="bf16") if gated else O.ref_fft_conv(q(u), k, N)
+            _, dkref = O.ref_grads(q(u), k, q(d), N)
+            for nm, want in (("out", ref), ("dk", dkref)):
+                a, b = alt[f"{nm}_{ci}_{B}"], base[f"{nm}_{ci}_{B}"]
+                what = f"fft {N} = {fac[0][0]} x {fac[1]}, B = {B}, one_launch = {one_launch}: {nm}"
+                assert rel(b, want) < 1.5e-2, f"{what}: default build against the oracle {rel(b, want):.3e}"
+                assert rel(a, want) < 1.5e-2, f"{what}: FFC_BIG_CHAIN=0 against the oracle {rel(a, want):.3e}"
+                assert rel(a, b.astype(np.float64)) < 1e-2, f"{what}: FFC_BIG_CHAIN=0 against the default build {rel(a, b.astype(np.float64)):.3e}"

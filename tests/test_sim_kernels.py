@@ -643,42 +643,92 @@ def test_levels_read_fp32_filter_and_write_fp32_dk(N, fac, Lk, dt):
         assert np.array_equal(BG.dk_from_pair(per_pass, N, y, H, Lk, fac), BG.dk_from_pair(pp_old, N, y, H, Lk, fac))
 
 
-@pytest.mark.parametrize("N,fac,L,gated", [(65536, ((16,), 4096), 30000, False), (131072, ((32,), 4096), 131072, True), (262144, ((64,), 4096), 131072, False),
-                                           (524288, ((128,), 4096), 100004, True)])
-def test_batch_of_one_keeps_half_of_the_level_rows(N, fac, L, gated):
+_HALF_ROW_CASES = [(65536, ((16,), 4096), 30000, False), (131072, ((32,), 4096), 131072, True), (262144, ((64,), 4096), 131072, False),
+                   (524288, ((128,), 4096), 100004, True)]
+
+
+@pytest.mark.parametrize("N,fac,L,gated,dt", [pytest.param(*c, dt, id=f"{c[0]}-fac{i}-{c[2]}-{c[3]}" + ("-fp16" if dt else ""))      # (bf16: the ids the cases had)
+                                              for dt in (0, 1) for i, c in enumerate(_HALF_ROW_CASES)])
+def test_batch_of_one_keeps_half_of_the_level_rows(N, fac, L, gated, dt):
     """round 6 (csrc/ffc_big.h BigArgs::half): ONE real row per head on the long side (B = 1; the filter and dk always) -- the level's rows
     k0 and K - k0 are conjugate mirrors, so the levels store / read the K / 2 + 1 rows k0 <= K / 2 only and the inner kernel convolves half
-    as many.  Forward (gated, ragged) and dk against the oracle, and against the full-row form of the same run (equal to rounding)."""
+    as many.  Forward (gated, ragged), du (conjugate inner convolution, inverse level with the pregate), dk and -- gated -- dpregate, dpostgate and
+    the gated dk against the oracle, and against the full-row form of the same run (equal to rounding); bf16 and fp16 (filter prescaled by 2^8).
+    fp16 gates: the GPU suite's (5e-3, dk 1e-2, x 1.5 gated) -- the simulator runs the same kernel body."""
     from flashfftconv import bigfft as BG
     rng = np.random.default_rng(N + L)
-    dt, H, B, M = 0, 2, 1, fac[1]
+    H, B, M = 2, 1, fac[1]
     K = fac[0][0]
     full, half = S.SimOps(), S.SimOps()
     half.half = True
     u, g1, g2, d = (rng.standard_normal((B, H, L)).astype(np.float32) for _ in range(4))
     k = (rng.standard_normal((H, L)) * 0.05).astype(np.float32)
     ub, g1b, g2b, db = (S.to_bits(x, dt) for x in (u, g1, g2, d))
-    outs, dks = [], []
+    outs, dks, grads = [], [], []
     for ops in (full, half):
-        kf = BG.kernel_fft(ops, dt, N, k, H, L, fac)
-        x = BG.levels_forward(ops, dt, N, ub, B, H, L, g1b if gated else None, fac)
+        r = S.big_forward_and_dk(ops, dt, N, fac, ub, db, k, g1b if gated else None, g2b if gated else None)
+        kf, x, y, xd = r["kf"], r["x"], r["y"], r["xd"]
         rows = K // 2 + 1 if ops.half else K
         assert x.shape == (2, H * rows, M) and kf.shape[0] == H * rows
-        y = ops.conv(dt, M, x, kf, False)
-        out = np.zeros_like(ub)
-        BG.levels_inverse(ops, dt, N, y, out, B, H, L, g2b if gated else None, None, fac)
-        outs.append(S.from_bits(out, dt))
-        xd = BG.levels_forward(ops, dt, N, db, B, H, L, None, fac)
-        xu = BG.levels_forward(ops, dt, N, ub, B, H, L, None, fac)
-        dks.append(BG.dk_from_slabs(ops, N, ops.dkf(dt, M, xd, xu), xu.shape[0], H, L, None, fac))
-    ref = O.ref_fft_conv_gated(q(u, dt), k, q(g1, dt), q(g2, dt), N, dtype="bf16") if gated else O.ref_fft_conv(q(u, dt), k, N)
-    _, dkref = O.ref_grads(q(u, dt), k, q(d, dt), N)
+        outs.append(S.from_bits(r["out"], dt))
+        dks.append(r["dk"])
+        # the gradients the way conv._big_backward / _big_backward_tail run them: levels over dout (* postgate), the conjugate inner
+        # convolution, the inverse level with the pregate at its store; gated: the same rows times u, the inner output times dout
+        xdg = BG.levels_forward(ops, dt, N, db, B, H, L, g2b, fac) if gated else xd
+        yd = ops.conv(dt, M, xdg, kf, True)
+        g = {"du": np.zeros_like(ub)}
+        BG.levels_inverse(ops, dt, N, yd, g["du"], B, H, L, g1b if gated else None, None, fac)
+        if gated:
+            g["dpregate"], g["dpostgate"] = np.zeros_like(ub), np.zeros_like(ub)
+            BG.levels_inverse(ops, dt, N, yd, g["dpregate"], B, H, L, ub, None, fac)
+            BG.levels_inverse(ops, dt, N, y, g["dpostgate"], B, H, L, db, None, fac)
+        g = {nm: S.from_bits(v, dt) for nm, v in g.items()}
+        if gated:
+            g["dk"] = BG.dk_from_slabs(ops, N, ops.dkf(dt, M, xdg, x), x.shape[0], H, L, None, fac)
+        grads.append(g)
+    ref = O.ref_fft_conv_gated(q(u, dt), k, q(g1, dt), q(g2, dt), N, dtype=NAME[dt]) if gated else O.ref_fft_conv(q(u, dt), k, N)
+    plain = dict(zip(("du", "dk"), O.ref_grads(q(u, dt), k, q(d, dt), N)))      # the oracle, once per form of the call
+    gref = dict(zip(("du", "dk", "dpregate", "dpostgate"), O.ref_grads(q(u, dt), k, q(d, dt), N, q(g1, dt), q(g2, dt)))) if gated else plain
+    dkref = plain["dk"]
     assert rel(outs[1], ref) < 1.5e-2 and rel(dks[1], dkref) < 1.5e-2
     assert rel(outs[1], outs[0].astype(np.float64)) < 1e-2 and rel(dks[1], dks[0].astype(np.float64)) < 1e-2
+    # fp16: the GPU suite's gates (5e-3, dk 1e-2, x 1.5 gated); bf16: the simulator's 1.5e-2 above
+    f = 1.5 if gated else 1.0
+    tol = {nm: 1.5e-2 if dt == 0 else f * (1e-2 if nm == "dk" else 5e-3) for nm in ("out", "du", "dk", "dpregate", "dpostgate")}
+    if dt == 1:
+        assert rel(outs[1], ref) < tol["out"] and rel(dks[1], dkref) < 1e-2, (rel(outs[1], ref), rel(dks[1], dkref))
+    for nm, got in grads[1].items():
+        e, e2 = rel(got, gref[nm]), rel(got, grads[0][nm].astype(np.float64))
+        assert e < tol[nm], f"{nm}: half rows against the oracle {e:.3e}"
+        assert rel(grads[0][nm], gref[nm]) < tol[nm], f"{nm}: full rows against the oracle"
+        assert e2 < 1e-2, f"{nm}: half rows against full rows {e2:.3e}"
     if K > 32:      # one launch per pass (ffc_outer_pass_r) == all passes in one launch (ffc_outer_pass_all): the forward rows bit for bit
         per_pass = S.SimOps(); per_pass.half = True; per_pass.one_launch = False
         xa = BG.levels_forward(half, dt, N, ub, B, H, L, None, fac)
         assert np.array_equal(xa, BG.levels_forward(per_pass, dt, N, ub, B, H, L, None, fac))
         out2 = np.zeros_like(ub)
         BG.levels_inverse(per_pass, dt, N, half.conv(dt, M, xa, BG.kernel_fft(half, dt, N, k, H, L, fac), False), out2, B, H, L, None, None, fac)
-        assert rel(S.from_bits(out2, dt), O.ref_fft_conv(q(u, dt), k, N)) < 1.5e-2
+        assert rel(S.from_bits(out2, dt), ref if not gated else O.ref_fft_conv(q(u, dt), k, N)) < (1.5e-2 if dt == 0 else 5e-3)      # ungated run: ungated gate
+
+
+# ---------------------------------------------------------------- the fused inner calls of the HBM-level path (SimOps.conv_kx / bwd_dk, the
+# product's ffc_conv_fwd_kx / ffc_conv_bwd_kx) on the half-row "head" counts H * (K / 2 + 1), H = 2: odd per head, no multiple of the
+# unit sizes the chunk policy was written for
+@pytest.mark.parametrize("hp", [18, 34, 66, 130])
+@pytest.mark.parametrize("dt", [0, 1])
+def test_fused_inner_calls_at_the_half_row_head_counts(hp, dt):
+    M = 8192                                       # the smallest inner size with the fused forms
+    rng = np.random.default_rng(hp + dt)
+    ops = S.SimOps()
+    x, xd = (S.to_bits(rng.standard_normal((2, hp, M)).astype(np.float32), dt) for _ in range(2))
+    xk = S.to_bits(rng.standard_normal((2, hp, M)).astype(np.float32) * 0.1, dt)
+    kf0 = ops.kfft_c(dt, M, xk, hp, 0.5)
+    y0 = ops.conv(dt, M, x, kf0, False)
+    y1, kf1, _ = ops.conv_kx(dt, M, x, xk, 0.5, False)
+    assert np.array_equal(kf0, kf1) and np.array_equal(y0, y1)
+    pair0 = ops.dkifft_c(M, ops.dkf(dt, M, xd, x), 2, hp, 0.25)
+    du0, _ = ops.bwd(dt, M, xd, x, kf0)
+    du1, pair1 = ops.bwd_dk(dt, M, xd, x, kf0, None, 0.25)
+    assert np.array_equal(du0, du1)
+    assert rel(S.from_bits(du1, dt), S.from_bits(ops.conv(dt, M, xd, kf0, True), dt).astype(np.float64)) < TOL[dt] / 4      # the conjugate forward launch: same rows
+    assert rel(S.from_bits(pair1, 0), S.from_bits(pair0, 0).astype(np.float64)) < 2e-3
