@@ -1,8 +1,7 @@
 #!/bin/bash
 # Build a tuning variant of the HIP library that differs from the product in a few translation units only:
-#   benchmarks/mkvariant.sh NAME "ffc_k_conv.hip ffc_k_bwdz.hip" -DFFC_KO=4 ...
+#   benchmarks/mkvariant.sh NAME "ffc_k_conv.hip ffc_k_bwdz.hip" -DFFC_OUTER_QUAD=0 ...
 # The product's objects are copied into lib/variants/NAME/obj, the listed units are recompiled with the extra flags.
-# (knock-out builds: FFC_SKIP_AGPR_CHECK=1 in the environment)
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 NAME=$1; TUS=$2; shift 2

@@ -143,13 +143,7 @@ int main(int argc, char** argv) {
   a.kf = d_kf; a.tab = d_blob; a.t = hp.tabs; a.H = H; a.B = 2; a.L = 16384; a.npair = 1;
   a.s_inv = 1.0f / 1024.0f; a.s_fwd = 1.0f; a.fast = 1;
   const int iters = argc > 2 ? atoi(argv[2]) : 200;
-  printf("phase-B probe, fft 32768 bf16, %d CUs, %d iterations x 32 tiles per CU%s\n", num_cu, iters,
-#if defined(FFC_KO)
-         "  [FFC_KO build: outer inverse twiddle removed]"
-#else
-         ""
-#endif
-  );
+  printf("phase-B probe, fft 32768 bf16, %d CUs, %d iterations x 32 tiles per CU\n", num_cu, iters);
   run<0>("A  8 waves x 256 regs, 2 tiles in lock-step (shipped fwd)", a, iters, d_cyc, num_cu, ticks_to_cycles);
   run<3>("D  8 waves x 256 regs, 1 tile at a time, twiddle resident", a, iters, d_cyc, num_cu, ticks_to_cycles);
   run<2>("C  8 waves x 128 regs, 1 tile at a time, twiddle from LDS", a, iters, d_cyc, num_cu, ticks_to_cycles);

@@ -19,16 +19,8 @@
 #include "ffc_layout.h"
 #include "ffc_plan.h"
 
-// activation rows go through non-temporal (streaming) global accesses: see DevB::g_r128_nt
-#ifndef FFC_STREAM_ROWS
-#define FFC_STREAM_ROWS 1
-#endif
 #ifndef FFC_FN
 #define FFC_FN inline __attribute__((always_inline))
-#endif
-// saved spectra (ConvArgs::zsave) written / read with streaming accesses (A/B: -DFFC_Z_STREAM=false keeps them cacheable)
-#ifndef FFC_Z_STREAM
-#define FFC_Z_STREAM true
 #endif
 
 namespace ffc {
@@ -175,13 +167,6 @@ struct Body {
   // the -Fi product is Fi times the negated imaginary operand (sign bits flipped: 4 v_xor per K-step)
   struct Mat2 { W4 w[2][2]; };
   static FFC_FN void load_mat2_issue(Mat2& m, const uint8_t* p, i32 lane) {
-#if defined(FFC_KO) && (FFC_KO & 2048)
-    // knock-out timing experiment (results wrong): no L2 traffic for the folded matrices -- every "load" is the lane id, so that the
-    // folded kernels' instruction stream can be timed without the cost of fetching the tables
-    { const u32 z = B::as_u32(B::i2f(lane));
-      for (int ms = 0; ms < 2; ms++) for (int f = 0; f < 2; f++) m.w[ms][f] = B::w4(z, z, z, z);
-      (void)p; return; }
-#endif
 #pragma unroll
     for (int ms = 0; ms < 2; ms++)
 #pragma unroll
@@ -260,9 +245,6 @@ struct Body {
   }
   // apply a chain8p result to accumulator rows 8*half + {0..7}
   static FFC_FN void apply8(A16& re, A16& im, int half, const F2 (&tr)[4], const F2 (&ti)[4]) {
-#if defined(FFC_KO) && (FFC_KO & 1)
-    return;      // timing experiment only: results are wrong
-#endif
 #pragma unroll
     for (int i = 0; i < 4; i++) B::template cmul2v<false>(re, im, 8 * half + 2 * i, tr[i], ti[i]);
   }
@@ -270,35 +252,19 @@ struct Body {
   // twiddle column: 32-point outer digit in phases A, 32-point last inner digit in the inverse twiddle).  The second half is the
   // first one times w^16 = (w^8)^2 -- four packed complex multiplies instead of a second chain with its three v_sin / v_cos pairs,
   // their argument preparation and the wait states behind them (6 -> 3 transcendental pairs per tile).
-  // FFC_CHAIN16=0: two chains, the round-4 form (A/B builds).
-#ifndef FFC_CHAIN16
-#define FFC_CHAIN16 1
-#endif
   // phases A: 32-point outer digit; not in the 128-VGPR kernels of fft 8192 (Geo<32,16,16> on a LEAN_OUTER backend: with the chain's
   // w^8 kept for the second half the allocator parked values in a0..a3 -- build.py check_agpr)
   static constexpr bool CHAIN16_A = GEO::N1 == 32 && (!B::LEAN_OUTER || GEO::N2 == 32);
-  // the per-tile outer stage (128-VGPR kernels, full-length rows) keeps two chains: with one, the recomputing full-length backward of
-  // fft 32768 spilled one value into a0 (build.py check_agpr)
-#ifndef FFC_CHAIN16_TILE
-#define FFC_CHAIN16_TILE 0
-#endif
   static FFC_FN void twiddle16(A16& re, A16& im, i32 base, i32 step, float sign, float scale,
                                int nmask = GEO::N - 1, float inv_n = 1.0f / (float)GEO::N) {
     F2 tr[4], ti[4];
-    if constexpr (FFC_CHAIN16 != 0) {
-      f32 c8, s8;
-      chain8p(base, step, sign, scale, tr, ti, nmask, inv_n, &c8, &s8);
-      apply8(re, im, 0, tr, ti);
-      const f32 c16 = c8 * c8 - s8 * s8, s16 = (c8 + c8) * s8;
+    f32 c8, s8;
+    chain8p(base, step, sign, scale, tr, ti, nmask, inv_n, &c8, &s8);
+    apply8(re, im, 0, tr, ti);
+    const f32 c16 = c8 * c8 - s8 * s8, s16 = (c8 + c8) * s8;
 #pragma unroll
-      for (int i = 0; i < 4; i++) B::cmulp(tr[i], ti[i], c16, s16, tr[i], ti[i]);
-      apply8(re, im, 1, tr, ti);
-    } else {
-      chain8p(base, step, sign, scale, tr, ti, nmask, inv_n);
-      apply8(re, im, 0, tr, ti);
-      chain8p(base + 16 * step, step, sign, scale, tr, ti, nmask, inv_n);
-      apply8(re, im, 1, tr, ti);
-    }
+    for (int i = 0; i < 4; i++) B::cmulp(tr[i], ti[i], c16, s16, tr[i], ti[i]);
+    apply8(re, im, 1, tr, ti);
   }
 #ifndef FFC_PK_GATE
 #define FFC_PK_GATE 1
@@ -444,11 +410,11 @@ struct Body {
   // slice (the columns it transforms in phases A/C, so no barrier is needed around the copies).
   // Inner-only sizes: row g = pair q*G+g, the single wave of the unit moves the whole tile.
   // 16-byte global accesses, 1 KiB contiguous per wave instruction when L % 8 == 0.
-  // Streaming rows (ConvArgs::stream, chosen by the host; FFC_STREAM=0/1 overrides it for A/B runs, benchmarks/prof_stream.py).
+  // Streaming rows = non-temporal global accesses, see DevB::g_r128_nt (ConvArgs::stream, chosen by the host; FFC_STREAM=0/1 overrides it
+  // for A/B runs, benchmarks/prof_stream.py).
   // Same process, same box, B16 H768: forward 16K 0.323 -> 0.313 ms, gated forward 32K 0.442 -> 0.410; ungated backward
   // 16K 0.667 -> 0.638, 32K 1.043 -> 1.025.  Not used in the gated backward, where the same workgroup reads u, dout and
   // the gates a second time as output gates (cfg3: 0.839 -> 0.865 with streaming).
-  static constexpr bool STREAM_ROWS = FFC_STREAM_ROWS != 0;
   static FFC_FN int64_t row_off(int b, bool ok, int64_t sb, int h, int L) { return (int64_t)(ok ? b : 0) * sb + (int64_t)h * L; }
   struct RowIO {
     const uint16_t* src[2]; const uint16_t* gate[2]; uint16_t* dst[2]; bool valid[2];
@@ -458,12 +424,9 @@ struct Body {
   // zero-initialised destination: consecutive loads never wait for each other, and the loads of the next pair
   // can stay in flight across phase C.
   static FFC_FN U4 gload8(const uint16_t* base, i32 n, int L, int fast, bool rowok) {
-#if defined(FFC_KO) && (FFC_KO & 2)
-    { U4 z; z.x = B::as_u32(B::i2f(n)); z.y = z.x; z.z = z.x; z.w = z.x; return z; }     // knock-out experiment: no row loads
-#endif
     // B::FAST_ONLY: kernel instantiations that are only launched on 16-byte-aligned tensors with L % 8 == 0 (the element-wise arm is
     // compiled out: with both arms in one kernel every load sits in its own flow block with a `s_waitcnt vmcnt(0)` at the merge)
-    if (B::FAST_ONLY || fast) return (STREAM_ROWS && fast == 2) ? B::g_r128_nt(base, B::imin(n, L - 8) >> 3) : B::g_r128(base, B::imin(n, L - 8) >> 3);
+    if (B::FAST_ONLY || fast) return fast == 2 ? B::g_r128_nt(base, B::imin(n, L - 8) >> 3) : B::g_r128(base, B::imin(n, L - 8) >> 3);
     u32 w[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) {
@@ -475,11 +438,8 @@ struct Body {
     return v;
   }
   static FFC_FN void gstore8(uint16_t* base, i32 n, int L, int fast, bool rowok, U4 v) {
-#if defined(FFC_KO) && (FFC_KO & 2)
-    if (B::as_f32(v.x) != B::as_f32(v.x) + 1.0f) return;      // knock-out experiment: (practically) never stores
-#endif
     if (B::FAST_ONLY || fast) {
-      if (STREAM_ROWS && fast == 2) B::g_w128_nt(base, n >> 3, v, (n < L) && rowok);
+      if (fast == 2) B::g_w128_nt(base, n >> 3, v, (n < L) && rowok);
       else B::g_w128(base, n >> 3, v, (n < L) && rowok);
       return;
     }
@@ -917,10 +877,8 @@ struct Body {
 #ifndef FFC_RP_HOIST
 #define FFC_RP_HOIST 1
 #endif
-// chunks per batch of the multi-pass row functions in the fast-only BACKWARD kernels (128-VGPR budget; the forward kernels take 4)
-#ifndef FFC_RP_BATCH_LEAN
-#define FFC_RP_BATCH_LEAN 2
-#endif
+  // chunks per batch of the multi-pass row functions in the fast-only BACKWARD kernels (128-VGPR budget; the forward kernels take 4)
+  static constexpr int RP_BATCH_LEAN = 2;
 // 0: the multi-pass backward always runs the kernel with the run-time access-width switch (A/B builds, bit-identity test)
 #ifndef FFC_RP_FASTK
 #define FFC_RP_FASTK 1
@@ -942,7 +900,7 @@ struct Body {
   }
   template <int NC, bool FASTP>
   static FFC_FN void rows_in_rp_t(const ConvArgs& a, int h, int pq, Unit un, Pass ps) {
-    constexpr int GB0 = (B::FAST_ONLY && B::LEAN_OUTER) ? FFC_RP_BATCH_LEAN : GB_RP;
+    constexpr int GB0 = (B::FAST_ONLY && B::LEAN_OUTER) ? RP_BATCH_LEAN : GB_RP;
     constexpr int GB = NC < GB0 ? NC : GB0;
     static_assert(NC % GB == 0, "row batch");
     const i32 lane = B::opaque(B::lane());
@@ -1047,7 +1005,7 @@ struct Body {
   static FFC_FN void rows_out_rp_t(const ConvArgs& a, int h, int pq, Unit un, Pass ps) {
     // batches of chunks: the earlier passes' sums (passes k0 > 0) and, on the last pass, the output gate of a batch are requested
     // together ahead of the work on them (round 4; before: the sums up front in the forward kernels only, the gate chunk by chunk)
-    constexpr int GBL = B::FAST_ONLY ? FFC_RP_BATCH_LEAN : GB_RP;
+    constexpr int GBL = B::FAST_ONLY ? RP_BATCH_LEAN : GB_RP;
     constexpr int GB = B::LEAN_OUTER ? (NC < GBL ? NC : GBL) : (NC < 4 ? NC : 4);
     static_assert(NC % GB == 0, "row batch");
     const i32 lane = B::opaque(B::lane());
@@ -1166,12 +1124,7 @@ struct Body {
       cmm<!FWD, false>(re, im, op, F1, ms_lim);
       if (FWD && !NOTW) {
         // s_fwd * W_N^{m*k1}: registers <-> rows k1 = 4*hi + {0..3} + 8*{0..3} (mod N1), lane/tile <-> column m
-        if constexpr (CHAIN16_A && FFC_CHAIN16_TILE) {              // both halves share the column m: one chain (twiddle16)
-          i32 m = j * 4 + (w * 128 * GEO::S1 + t);
-          i32 k0 = hi * 4;
-          if constexpr (RP) twiddle16(re, im, m * (k0 * ps.R + ps.k0), m * ps.R, -1.0f, s_fwd, GEO::N * ps.R - 1, 1.0f / (float)(GEO::N * ps.R));
-          else twiddle16(re, im, m * k0, m, -1.0f, s_fwd);
-        } else
+        // (two chains here: with one -- twiddle16 -- the recomputing full-length backward of fft 32768 spilled one value into a0, build.py check_agpr)
 #pragma unroll
         for (int half = 0; half < 2; half++) {     // accumulator registers 0-7 / 8-15 (rows +16)
           const int s1 = (16 * half) / GEO::N1;     // second half: next column set when N1 == 16
@@ -1426,14 +1379,8 @@ struct Body {
   template <bool FWD, bool HALF, bool RP = false, bool DIN = false, bool NOTW = false>
   static FFC_FN void outer_stage(int L, Unit un, float s_fwd = 1.0f, Pass ps = Pass()) {
     if constexpr (DIN) { outer_stage_pair<FWD, HALF, RP, true, NOTW>(L, un, s_fwd, ps); return; }
-#if defined(FFC_KO) && (FFC_KO & 8)
-    return;
-#endif
-#ifndef FFC_LEAN_TILE
-#define FFC_LEAN_TILE 0
-#endif
     // backward kernels (128-VGPR budget): the tile-pair form only fits with one K-step of raw rows (half-empty outer digit)
-    if constexpr (B::LEAN_OUTER && (FFC_LEAN_TILE || !(FWD && HALF && GEO::N1 == 32))) outer_stage_tile<FWD, HALF, RP, NOTW>(L, un, s_fwd, ps);
+    if constexpr (B::LEAN_OUTER && !(FWD && HALF && GEO::N1 == 32)) outer_stage_tile<FWD, HALF, RP, NOTW>(L, un, s_fwd, ps);
     // (HALF kernels only: same box, round 5 -- forward -1 ... -3 % at L <= N/2 (config 2 0.4474 -> 0.4334 ms with the chain change, gated
     // fft 16384 -2.8 %), but the full-length spectrum-saving forward came out 5 % SLOWER with it (0.695 -> 0.730 ms, no spills: 28 more
     // live registers through phase C), the full-length plain forward 1.5 % faster: profiles/r05_ab_kernels.txt)
@@ -1721,10 +1668,8 @@ struct Body {
   struct KfRegs { U4 v[4]; };
   // A spectrum tile in global memory: (re, im)-interleaved dtype pairs in the k_f tile layout (16-byte accesses, 1 KiB
   // per wave instruction).  Used for the backward kernels' scratch and for the spectra the forward pass saves.
+  static constexpr bool Z_STREAM = true;      // the spectra saved for the backward pass (ConvArgs::zsave) are written / read with streaming accesses
   static FFC_FN void z_store(void* zs, int tau, const A16& re, const A16& im, bool nt = false) {
-#if defined(FFC_KO) && (FFC_KO & 64)
-    return;        // knock-out timing experiment: no spectrum scratch traffic (results wrong)
-#endif
     const i32 lane = B::opaque(B::lane());
     const i32 c = lane & 31, hi = lane >> 5;
 #pragma unroll
@@ -1739,10 +1684,6 @@ struct Body {
   static FFC_FN void z_load(const void* zs, int tau, KfRegs& z, bool nt = false) {
     const i32 lane = B::opaque(B::lane());
     const i32 c = lane & 31, hi = lane >> 5;
-#if defined(FFC_KO) && (FFC_KO & 64)
-    for (int rq = 0; rq < 4; rq++) { z.v[rq].x = B::as_u32(B::i2f(c + tau)); z.v[rq].y = z.v[rq].x; z.v[rq].z = z.v[rq].x; z.v[rq].w = z.v[rq].x; }
-    return;
-#endif
     if (nt) {
 #pragma unroll
       for (int rq = 0; rq < 4; rq++) z.v[rq] = B::g_r128_nt(zs, ((hi + (tau * 8 + 2 * rq)) * 32 + c));
@@ -1768,10 +1709,6 @@ struct Body {
     const i32 lane = B::opaque(B::lane());
     const i32 c = lane & 31, hi = lane >> 5;
     const uint8_t* kfh = (const uint8_t*)a.kf + (int64_t)h * (GEO::NT * 1024 * 4);
-#if defined(FFC_KO) && (FFC_KO & 4)
-    for (int rq = 0; rq < 4; rq++) { k.v[rq].x = B::as_u32(B::i2f(c + tau)); k.v[rq].y = k.v[rq].x; k.v[rq].z = k.v[rq].x; k.v[rq].w = k.v[rq].x; }
-    return;
-#endif
     if (a.flags & 2) {      // tuning flag: k_f as a streaming (non-temporal) read
 #pragma unroll
       for (int rq = 0; rq < 4; rq++) k.v[rq] = B::g_r128_nt(kfh, ((hi + (tau * 8 + 2 * rq)) * 32 + c));
@@ -1787,7 +1724,7 @@ struct Body {
     A16 re, im;
     tile_fwd<true, IP>(tau, R, un, re, im, ip);
     if constexpr (SZ) {      // (single-tile sizes: zs may be null -- the gated forward that keeps only the output before the postgate, ConvArgs::yraw)
-      if (GEO::OUTER || zs) z_store(zs, 0, re, im, FFC_Z_STREAM);
+      if (GEO::OUTER || zs) z_store(zs, 0, re, im, Z_STREAM);
     }
     // (x) k_f
 #pragma unroll
@@ -1959,13 +1896,7 @@ struct Body {
   // SZ (compile time: phase B must stay one basic block): store both tiles' spectra at zs (ConvArgs::zsave)
   // FFC_FOLD_TW form of inner_tile2 (see tile_fwd): every stage of either tile multiplies by its own per-(stage, tile) matrix from L2 with the
   // outer twiddle folded in; the loads of a stage's two matrices are requested one stage ahead.  No oi_twiddle, and phase A ran without
-  // its twiddle (outer_stage<.., NOTW>).  LDSTW: inner twiddle streamed from LDS instead of the 32 resident registers.
-#ifndef FFC_FOLD_LDSTW
-#define FFC_FOLD_LDSTW 0
-#endif
-#ifndef FFC_FOLD_FWD
-#define FFC_FOLD_FWD 1      // (with FFC_FOLD_TW) 0: only the saved-spectra backward folds, the forward kernels keep the chains
-#endif
+  // its twiddle (outer_stage<.., NOTW>).
   template <bool SZ>
   static FFC_FN void inner_tile2_fold(const ConvArgs& a, int h, int tauA, const InnerRegs& R, Unit un, uint8_t* zs) {
     static_assert(CAN_FOLD, "folded outer twiddle: fft 32768 geometry");
@@ -1984,8 +1915,8 @@ struct Body {
     load_mat2_issue(FBa, fold + (1 * GEO::NT + tauA) * 6144, lane);
     load_mat2_issue(FBb, fold + (1 * GEO::NT + tauB) * 6144, lane);
     A16 reA, imA, reB, imB;
-    auto tw_fwd = [&](A16& re, A16& im) { if constexpr (FFC_FOLD_LDSTW != 0) cmul_lds<false>(re, im, GEO::L_TW); else cmul(re, im, R.tw); };
-    auto tw_inv = [&](A16& re, A16& im) { if constexpr (FFC_FOLD_LDSTW != 0) cmul_lds<true>(re, im, GEO::L_TW); else cmul_conj(re, im, R.tw); };
+    auto tw_fwd = [&](A16& re, A16& im) { cmul(re, im, R.tw); };
+    auto tw_inv = [&](A16& re, A16& im) { cmul_conj(re, im, R.tw); };
     // stage a
     reA = B::a16_zero(); imA = B::a16_zero();
     cmm2<true>(reA, imA, opA, FAa);
@@ -2001,7 +1932,7 @@ struct Body {
     tw_fwd(reB, imB); to_op(reB, imB, opB);
     reB = B::a16_zero(); imB = B::a16_zero();
     cmm2<false>(reB, imB, opB, FBb);
-    if constexpr (SZ) { z_store(zs, tauA, reA, imA, FFC_Z_STREAM); z_store(zs, tauB, reB, imB, FFC_Z_STREAM); }
+    if constexpr (SZ) { z_store(zs, tauA, reA, imA, Z_STREAM); z_store(zs, tauB, reB, imB, Z_STREAM); }
     // (x) k_f, inverse stage b
     kf_mul<SZ>(a, kfA, reA, imA); to_op(reA, imA, opA);
     Mat2 GAa, GAb;
@@ -2022,11 +1953,8 @@ struct Body {
     tile_store(tauA, R, reA, imA);
     tile_store(tauB, R, reB, imB);
   }
-  // one tile at a time (FFC_FOLD_ONE: the L <= N/2 forward kernels, whose next pair's rows wait in 32 registers across phase B -- with two
+  // one tile at a time (HALFK: the L <= N/2 forward kernels, whose next pair's rows wait in 32 registers across phase B -- with two
   // tiles' matrices in flight they spilled 60 .. 170 registers)
-#ifndef FFC_FOLD_ONE
-#define FFC_FOLD_ONE 2      // 0: two tiles in lock-step everywhere, 1: one tile at a time everywhere, 2: one at a time in the L <= N/2 kernels only
-#endif
   template <bool SZ>
   static FFC_FN void inner_tile1_fold(const ConvArgs& a, int h, int tau, const InnerRegs& R, Unit un, uint8_t* zs) {
     static_assert(CAN_FOLD, "folded outer twiddle: fft 32768 geometry");
@@ -2043,16 +1971,16 @@ struct Body {
     re = B::a16_zero(); im = B::a16_zero();
     cmm2<true>(re, im, op, FA);
     load_mat2_issue(GB, fold + (2 * GEO::NT + tau) * 6144, lane);
-    if constexpr (FFC_FOLD_LDSTW != 0) cmul_lds<false>(re, im, GEO::L_TW); else cmul(re, im, R.tw);
+    cmul(re, im, R.tw);
     to_op(re, im, op);
     re = B::a16_zero(); im = B::a16_zero();
     cmm2<false>(re, im, op, FB);
     load_mat2_issue(GA, fold + (3 * GEO::NT + tau) * 6144, lane);
-    if constexpr (SZ) z_store(zs, tau, re, im, FFC_Z_STREAM);
+    if constexpr (SZ) z_store(zs, tau, re, im, Z_STREAM);
     kf_mul<SZ>(a, kf, re, im); to_op(re, im, op);
     re = B::a16_zero(); im = B::a16_zero();
     cmm2<true>(re, im, op, GB);
-    if constexpr (FFC_FOLD_LDSTW != 0) cmul_lds<true>(re, im, GEO::L_TW); else cmul_conj(re, im, R.tw);
+    cmul_conj(re, im, R.tw);
     to_op(re, im, op);
     re = B::a16_zero(); im = B::a16_zero();
     cmm2<true>(re, im, op, GA);
@@ -2062,7 +1990,7 @@ struct Body {
   static FFC_FN void inner_tile2(const ConvArgs& a, int h, int tauA, const InnerRegs& R, Unit un, Pass ps = Pass(), uint8_t* zs = nullptr) {
     static_assert(GEO::N3 == GEO::N2 && GEO::OUTER, "inner_tile2: fused sizes with one inner matrix");
     if constexpr (FOLD) {
-      if constexpr (FFC_FOLD_ONE == 1 || (FFC_FOLD_ONE == 2 && HALFK)) { inner_tile1_fold<SZ>(a, h, tauA, R, un, zs); inner_tile1_fold<SZ>(a, h, tauA + 1, R, un, zs); }
+      if constexpr (HALFK) { inner_tile1_fold<SZ>(a, h, tauA, R, un, zs); inner_tile1_fold<SZ>(a, h, tauA + 1, R, un, zs); }
       else inner_tile2_fold<SZ>(a, h, tauA, R, un, zs);
       return;
     }
@@ -2086,7 +2014,7 @@ struct Body {
     cmul(reB, imB, R.tw); to_op(reB, imB, opB);
     reB = B::a16_zero(); imB = B::a16_zero();
     cmm<false, false>(reB, imB, opB, R.F2);
-    if constexpr (SZ) { z_store(zs, tauA, reA, imA, FFC_Z_STREAM); z_store(zs, tauB, reB, imB, FFC_Z_STREAM); }     // spectrum kept for the backward pass
+    if constexpr (SZ) { z_store(zs, tauA, reA, imA, Z_STREAM); z_store(zs, tauB, reB, imB, Z_STREAM); }     // spectrum kept for the backward pass
     // (x) k_f, inverse stage b
     kf_mul<SZ>(a, kfA, reA, imA); to_op(reA, imA, opA);
     reA = B::a16_zero(); imA = B::a16_zero();
@@ -2141,7 +2069,7 @@ struct Body {
     reB = B::a16_zero(); imB = B::a16_zero();
     cmm2<false>(reB, imB, opB, FB);
     load_mat2_issue(GA, fold + (3 * GEO::NT + tau) * 6144, lane);
-    if constexpr (SZ) { z_store(zsA, tau, reA, imA, FFC_Z_STREAM); z_store(zsB, tau, reB, imB, FFC_Z_STREAM); }
+    if constexpr (SZ) { z_store(zsA, tau, reA, imA, Z_STREAM); z_store(zsB, tau, reB, imB, Z_STREAM); }
     {
       CT16 k;
 #pragma unroll
@@ -2190,7 +2118,7 @@ struct Body {
     cmul(reB, imB, R.tw); to_op(reB, imB, opB);
     reB = B::a16_zero(); imB = B::a16_zero();
     cmm<false, false>(reB, imB, opB, R.F2);
-    if constexpr (SZ) { z_store(zsA, tau, reA, imA, FFC_Z_STREAM); z_store(zsB, tau, reB, imB, FFC_Z_STREAM); }     // spectra kept for the backward pass
+    if constexpr (SZ) { z_store(zsA, tau, reA, imA, Z_STREAM); z_store(zsB, tau, reB, imB, Z_STREAM); }     // spectra kept for the backward pass
     // (x) k_f: unpacked once
     {
       CT16 k;
@@ -2222,7 +2150,7 @@ struct Body {
       const i32 lane = B::opaque(B::lane());
       const i32 c = lane & 31, hi = lane >> 5;
       const i32 sUl = c / GEO::N2, mlane = (c % GEO::N2) * GEO::N3;
-      if constexpr (GEO::N3 == 32 && FFC_CHAIN16 != 0) {      // fft 16384: the second half is the first one times w^16 (see twiddle16)
+      if constexpr (GEO::N3 == 32) {      // fft 16384: the second half is the first one times w^16 (see twiddle16)
         i32 k1 = sUl * GEO::SV + tau * GEO::G;
         F2 tr[4], ti[4];
         f32 c8, s8;
@@ -2258,9 +2186,6 @@ struct Body {
   // waves of the workgroup are then free to drift apart, one unit's global loads / stores overlap another's math
   // instead of all eight meeting at every phase boundary.
   static FFC_FN void unit_barrier() {
-#if defined(FFC_KO) && (FFC_KO & 32)
-    B::lds_fence(); return;
-#endif
     if constexpr (GEO::NW > 1) B::barrier();
     else B::lds_fence();
   }
@@ -2276,12 +2201,8 @@ struct Body {
     // (profiles/r01_phase_cycles.txt).
     constexpr bool PREFETCH = HALF && !RP;    // full-length rows: 64 row registers on top of phase C would spill
     // FFC_FOLD_TW: forward / dx kernels of single-pass fft 32768 (not the frequency-sparse, profiling or dynamically scheduled variants)
-    constexpr bool FOLDF = CAN_FOLD && !RP && !SP && !PROF && !B::LEAN_OUTER && FFC_FOLD_FWD != 0;
-#if defined(FFC_NO_CROSS)
-    constexpr bool CROSS = false;
-#else
+    constexpr bool FOLDF = CAN_FOLD && !RP && !SP && !PROF && !B::LEAN_OUTER;
     constexpr bool CROSS = !SP && !RP && !PROF && !B::LEAN_OUTER && GEO::N3 == GEO::N2 && GEO::NW > 1 && GEO::UPW >= 2;
-#endif
     // (a split prefetch for the full-length kernels -- first half of the next pair's rows early, second half at the top of
     // the iteration -- was measured: the 32768 kernel then needs 256 VGPRs + 16 spilled and runs the same, 8192 gains 2-4 %;
     // not kept)
@@ -2303,12 +2224,8 @@ struct Body {
     // they compete for the same unit (MFMA against MFMA, twiddle VALU against twiddle VALU), and the kernel ran 12 % slower.
     const bool second = B::wave() >= 4;
     // (fft 4096, one wave per unit and no barriers between the waves: +3 % with priorities, so only where waves share a unit;
-    // same-box A/B: forward -2.1 % at fft 32768, -1.2 % at 16384, -2 % at 8192; -DFFC_NO_PRIO builds the kernels without)
-#if defined(FFC_NO_PRIO)
-#define FFC_PRIO(x)
-#else
+    // same-box A/B: forward -2.1 % at fft 32768, -1.2 % at 16384, -2 % at 8192)
 #define FFC_PRIO(x) if constexpr (GEO::NW > 1) B::template setprio<x>();
-#endif
 #pragma unroll 1
     for (int it = 0; it < iters; it++) {
       const int p = p0 + (RP ? it / npass : it) * GEO::UPW + u;
@@ -2359,9 +2276,6 @@ struct Body {
         // anything the compiler spills would wait behind it.  k_f is prefetched one tile ahead only here.
         InnerRegs R;
         load_inner(R, un);
-#if defined(FFC_KO) && (FFC_KO & 16)
-        if (a.L < 0)
-#endif
         if constexpr (SP) {
           Mat Fs;
           lds_mat_sp(Fs);

@@ -42,10 +42,6 @@ struct DevB {
   static constexpr bool HAS_TR = true;
   // element-wise complex multiply of two accumulator tuples (x (x) t or x (x) conj t): whole-vector fp32 ops,
   // which gfx950 legalises to v_pk_mul_f32 / v_pk_fma_f32 on aligned register pairs
-#ifndef FFC_NO_PK
-#define FFC_NO_PK 0
-#endif
-#if !FFC_NO_PK
   template <bool CONJ> static FFC_FN void cmul16(A16& re, A16& im, const A16& tr, const A16& ti) {
     const A16 a = re, b = im;
     if (!CONJ) { re = a * tr - b * ti; im = a * ti + b * tr; }
@@ -74,41 +70,6 @@ struct DevB {
     wr = wr + (a2 * zr + b2 * zi);
     wi = wi + (b2 * zr - a2 * zi);
   }
-#else
-  // scalar fp32 variant of the same helpers (A/B of packed vs plain VALU next to MFMAs: MI355X_MICROARCH.md prices a
-  // v_pk_fma_f32 beside MFMAs well above two v_fma_f32)
-  static FFC_FN f32 sfma(f32 a, f32 b, f32 c) { return __builtin_fmaf(a, b, c); }
-  template <bool CONJ> static FFC_FN void cmul16(A16& re, A16& im, const A16& tr, const A16& ti) {
-#pragma unroll
-    for (int r = 0; r < 16; r++) {
-      const f32 a = re[r], b = im[r];
-      if (!CONJ) { re[r] = sfma(a, tr[r], -(b * ti[r])); im[r] = sfma(a, ti[r], b * tr[r]); }
-      else { re[r] = sfma(a, tr[r], b * ti[r]); im[r] = sfma(b, tr[r], -(a * ti[r])); }
-    }
-  }
-  struct F2 { f32 x, y; };
-  static FFC_FN F2 f2(f32 a, f32 b) { F2 v; v.x = a; v.y = b; return v; }
-  static FFC_FN f32 f2_lo(F2 v) { return v.x; }
-  static FFC_FN f32 f2_hi(F2 v) { return v.y; }
-  static FFC_FN void cmulp(F2 xr, F2 xi, f32 wr, f32 wi, F2& yr, F2& yi) {
-    yr.x = sfma(xr.x, wr, -(xi.x * wi)); yr.y = sfma(xr.y, wr, -(xi.y * wi));
-    yi.x = sfma(xr.x, wi, xi.x * wr); yi.y = sfma(xr.y, wi, xi.y * wr);
-  }
-  template <bool CONJ>
-  static FFC_FN void cmul2v(A16& re, A16& im, int r0, F2 tr, F2 ti) {
-    const f32 t_r[2] = {tr.x, tr.y}, t_i[2] = {ti.x, ti.y};
-#pragma unroll
-    for (int q = 0; q < 2; q++) {
-      const f32 a = re[r0 + q], b = im[r0 + q];
-      if (!CONJ) { re[r0 + q] = sfma(a, t_r[q], -(b * t_i[q])); im[r0 + q] = sfma(a, t_i[q], b * t_r[q]); }
-      else { re[r0 + q] = sfma(a, t_r[q], b * t_i[q]); im[r0 + q] = sfma(b, t_r[q], -(a * t_i[q])); }
-    }
-  }
-  static FFC_FN void cmac2_conj(F2& wr, F2& wi, const A16& a, const A16& b, int r0, F2 zr, F2 zi) {
-    wr.x = wr.x + sfma(a[r0], zr.x, b[r0] * zi.x); wr.y = wr.y + sfma(a[r0 + 1], zr.y, b[r0 + 1] * zi.y);
-    wi.x = wi.x + sfma(b[r0], zr.x, -(a[r0] * zi.x)); wi.y = wi.y + sfma(b[r0 + 1], zr.y, -(a[r0 + 1] * zi.y));
-  }
-#endif
   // Accumulation registers a0..a127 addressed by number (see Modes::WAcc).  The kernel marks them used once
   // (agpr_reserve) so that the kernel descriptor allocates them; the compiler itself never places values there
   // (MFMAs are kept in VGPR form, build flag -mllvm --amdgpu-mfma-vgpr-form; build.py checks the disassembly).
@@ -126,16 +87,6 @@ struct DevB {
     return x;
   }
   template <int I> static FFC_FN void agpr_set(f32 x) { asm volatile("v_accvgpr_write_b32 a%c0, %1" ::"n"(I), "v"(x)); }
-  // Round 6: acc[I0 .. I0+15] (accumulation registers) += A x B, bf16 operands.  The dk_f sums are accumulated by the matrix pipe (Modes::
-  // w_acc_tile: B = the products D (x) conj Z rounded to bf16, A = a permuted identity), so the VALU never shuttles them through
-  // v_accvgpr_read / v_accvgpr_write.  Inline asm (the compiler keeps its own MFMAs in VGPR form and must not see a0..a127): the wait states
-  // are ours (cdna_hip_programming.md 5.7 item 2) -- `s_nop 1` covers the VALU-written A / B operands; an MFMA that takes the previous
-  // one's destination whole as C needs none; readers of the sums call mfma_settle() first.
-  template <int I0> static FFC_FN void mfma_acc_bf16(const W4& a, const W4& b) {
-    asm volatile("s_nop 1\n\tv_mfma_f32_32x32x16_bf16 a[%c2:%c3], %0, %1, a[%c2:%c3]" ::"v"(a), "v"(b), "n"(I0), "n"(I0 + 15));
-  }
-  // an MFMA's destination -> any reader other than the next accumulating MFMA: 12 wait states for the 8-pass 32x32x16 (ibid.)
-  static FFC_FN void mfma_settle() { asm volatile("s_nop 15"); }
   // keep a load-defined MFMA operand in architectural VGPRs (the allocator may otherwise place it in the
   // accumulation registers, which hold the dk_f partial sums in the backward kernels)
   static FFC_FN void pin(W4& x) { asm("" : "+v"(x)); }
@@ -146,16 +97,7 @@ struct DevB {
   static FFC_FN void cmul2(A16& re, A16& im, int r0, f32 tr0, f32 tr1, f32 ti0, f32 ti1) {
     cmul2v<CONJ>(re, im, r0, f2(tr0, tr1), f2(ti0, ti1));
   }
-#if !FFC_NO_PK
   static FFC_FN A16 a16_scale(const A16& a, float s) { return a * s; }
-#else
-  static FFC_FN A16 a16_scale(const A16& a, float s) {
-    A16 o;
-#pragma unroll
-    for (int r = 0; r < 16; r++) o[r] = a[r] * s;
-    return o;
-  }
-#endif
   static FFC_FN A16 a16_zero() { A16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; return z; }
   static FFC_FN W4 w4(u32 a, u32 b, u32 c, u32 e) { W4 v = {a, b, c, e}; return v; }
 
@@ -213,11 +155,7 @@ struct DevB {
   // v_sin/v_cos run on the transcendental unit; consumers scheduled right behind them (packed f32 math in
   // particular) were observed to read stale operands on gfx950 (timing-dependent 1-3% errors, caught by a
   // run-to-run determinism check).  An opaque asm with wait states orders them conservatively.
-#ifndef FFC_NO_SETTLE
   static FFC_FN void settle(f32& a, f32& b) { asm volatile("s_nop 4" : "+v"(a), "+v"(b)); }
-#else
-  static FFC_FN void settle(f32&, f32&) {}      // hazard experiment (benchmarks/hazard_probe.py): no wait states
-#endif
   static FFC_FN f32 i2f(i32 a) { return (float)a; }
   static FFC_FN f32 cos_rev(f32 x) { return __builtin_amdgcn_cosf(x); }   // v_cos_f32: argument in revolutions
   static FFC_FN f32 sin_rev(f32 x) { return __builtin_amdgcn_sinf(x); }

@@ -25,20 +25,6 @@ __global__ __launch_bounds__(256) void mul_rows_kernel(const uint16_t* __restric
 }
 
 
-#if defined(FFC_BWD_PROF)
-// profiling variant only (build.py --variant bwdprof -DFFC_BWD_PROF): per-phase s_memtime sums, [workgroup][wave][16]
-static unsigned long long* ffc_bwd_prof_buffer() {
-  static unsigned long long* buf = nullptr;
-  if (!buf && hipMalloc((void**)&buf, 8192 * 8 * 16 * 8) != hipSuccess) buf = nullptr;
-  return buf;
-}
-extern "C" int ffc_debug_bwd_prof(unsigned long long* out_host, int64_t n_words) {
-  unsigned long long* b = ffc_bwd_prof_buffer();
-  if (!b || n_words > 8192 * 8 * 16) return ffc_fail("no profile buffer");
-  return hipMemcpy(out_host, b, n_words * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : ffc_fail("copy failed");
-}
-#endif
-
 // Fused backward: du = pregate * corr(dout*postgate, k), dpre = u * corr(...) (nullable, gated only) and the
 // dk_f partial sums in `ws` (same layout as ffc_conv_bwd_dkf; finish with ffc_kernel_ifft_grad).
 extern "C" int ffc_conv_fwd(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate, void* y,
@@ -92,7 +78,7 @@ static int conv_bwd_impl(const ffc_plan* p, const void* dout, const void* u, con
   ffc_choose_chunks(p, a.H, a.npair, &a.nchunk, &a.ppc);
   a.persist = ffc_persist(p);
   a.R = p->hp.R;
-  a.stream = p->env_stream >= 0 ? p->env_stream : ((!pregate && !postgate && p->hp.R == 1) ? 1 : 0);    // see Body::STREAM_ROWS
+  a.stream = p->env_stream >= 0 ? p->env_stream : ((!pregate && !postgate && p->hp.R == 1) ? 1 : 0);    // see Body::gload8
   a.flags = p->env_flags;                        // tuning flags: 2 = k_f streamed, 4 = scratch streamed
   d.dout = dout; d.ws = (float*)ws; d.du = du; d.dpre = dpre; d.zscratch = ffc_zscratch(p, ws, a.H, a.nchunk);
   // dk from the same launch (Modes::dk_tail / dk_tail_multi): the workgroup owns all pairs of its head, fft 16384 / 32768 (8192 on request)
@@ -141,9 +127,6 @@ static int conv_bwd_impl(const ffc_plan* p, const void* dout, const void* u, con
     d.dpost = nullptr; d.yraw = nullptr; dpost = nullptr;
   }
   if (d.dpost && ((((uintptr_t)dpost) | (uintptr_t)yraw) & 15)) a.fast = 0;
-#if defined(FFC_BWD_PROF)
-  a.prof = ffc_bwd_prof_buffer();
-#endif
   // fused sizes >= 4096 on saved spectra: the ZM = 1 kernels (ffc_k_bwdz.hip); everything else from this unit
   int rc = (zin && p->hp.N1 > 1) ? ffc_bwdz_launch(p->hp.N, p->hp.dtype, d, (hipStream_t)stream)
                                  : ffc_dispatch<BwdLaunchZ<0>::T>(p->hp.N, p->hp.dtype, d, (hipStream_t)stream);

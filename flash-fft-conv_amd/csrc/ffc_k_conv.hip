@@ -2,12 +2,10 @@
 #include "ffc_dev.h"
 using namespace ffc;
 
+static constexpr int SMALL_WAVES = 2;      // waves per SIMD the single-tile kernels (no outer digit) are compiled for
 // SZ: the forward that also stores the pairs' spectra for the backward pass (ConvArgs::zsave; fused sizes with an outer digit)
-#ifndef FFC_SMALL_WAVES
-#define FFC_SMALL_WAVES 2
-#endif
 template <class GEO, int DT, bool HALF, bool SZ = false, bool SP = false>
-__global__ __launch_bounds__(GEO::WGW * 64, GEO::OUTER ? 2 : FFC_SMALL_WAVES) void conv_kernel(ConvArgs a) {
+__global__ __launch_bounds__(GEO::WGW * 64, GEO::OUTER ? 2 : SMALL_WAVES) void conv_kernel(ConvArgs a) {
   using BD = Body<DevB, GEO, DT>;
   if constexpr (GEO::OUTER && GEO::NW == 1) {
     // One wave per unit (fft 4096): persistent workgroups, one per CU, walk the (head, chunk) jobs with a stride of

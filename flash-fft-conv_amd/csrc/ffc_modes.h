@@ -8,9 +8,6 @@
 // Pair packing keeps working for dk: with z_u = u_a + i u_b and z_d = d_a + i d_b,
 //   Re iFFT( Z_d * conj(Z_u) ) = corr(d_a,u_a) + corr(d_b,u_b).
 #pragma once
-#ifndef FFC_IP_LEAN
-#define FFC_IP_LEAN 1      // 0: the pass's tables resident in 80 registers (round 5: 34 - 43 registers spilled; A/B builds)
-#endif
 #include "ffc_body.h"
 
 namespace ffc {
@@ -83,9 +80,6 @@ struct DkArgs {
   int R;               // > 1: multi-pass size (struct Pass); slab rows are (head, pass)
 };
 
-#ifndef FFC_WREG
-#define FFC_WREG 4
-#endif
 template <class B, class GEO, int DT>
 struct Modes : Body<B, GEO, DT> {
   using BD = Body<B, GEO, DT>;
@@ -358,7 +352,7 @@ struct Modes : Body<B, GEO, DT> {
             k_rows_in_rp(a, unit_id, un, ps);
             B::lds_fence();
             A16 re, im;
-            BD::template tile_fwd<true, true, false, FFC_IP_LEAN != 0>(0, R, un, re, im, &ip);
+            BD::template tile_fwd<true, true, false, true>(0, R, un, re, im, &ip);
             kf_store_flat(a, unit_id * a.R + k0, re, im, a.H * a.R);
             B::lds_fence();
           }
@@ -428,45 +422,6 @@ struct Modes : Body<B, GEO, DT> {
   }
   using BD::z_store;
   using BD::z_load;
-  // previous partial sums of a tile, issued at the start of the tile so the latency overlaps tile_fwd
-  struct WOld { U4 v[4][2]; };
-  static FFC_FN void w_load_old(const float* slab, int tau, bool first, WOld& o) {
-    const i32 lane = B::opaque(B::lane());
-    const i32 c = lane & 31, hi = lane >> 5;
-#pragma unroll
-    for (int rq = 0; rq < 4; rq++) {
-      i32 idx = ((hi + (tau * 8 + 2 * rq)) * 32 + c) * 2;
-      o.v[rq][0] = B::g_r128p(slab, idx, !first ? B::ptrue() : B::pfalse());
-      o.v[rq][1] = B::g_r128p(slab, idx + 1, !first ? B::ptrue() : B::pfalse());
-    }
-  }
-  static FFC_FN void w_update(float* slab, int tau, const WOld& o, const typename BD::KfRegs& zv, const A16& re, const A16& im) {
-    const i32 lane = B::opaque(B::lane());
-    const i32 c = lane & 31, hi = lane >> 5;
-#pragma unroll
-    for (int rq = 0; rq < 4; rq++) {
-      i32 idx = ((hi + (tau * 8 + 2 * rq)) * 32 + c) * 2;
-      u32 wv[4] = {zv.v[rq].x, zv.v[rq].y, zv.v[rq].z, zv.v[rq].w};
-      f32 wr[4], wi[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        const int r = 4 * rq + q;
-        f32 ur = B::template unpack_lo<DT>(wv[q]), ui = B::template unpack_hi<DT>(wv[q]);
-        wr[q] = re[r] * ur + im[r] * ui;
-        wi[q] = im[r] * ur - re[r] * ui;
-      }
-      const U4& o0 = o.v[rq][0]; const U4& o1 = o.v[rq][1];       // zeros on the first pair
-      wr[0] = wr[0] + B::as_f32(o0.x); wi[0] = wi[0] + B::as_f32(o0.y);
-      wr[1] = wr[1] + B::as_f32(o0.z); wi[1] = wi[1] + B::as_f32(o0.w);
-      wr[2] = wr[2] + B::as_f32(o1.x); wi[2] = wi[2] + B::as_f32(o1.y);
-      wr[3] = wr[3] + B::as_f32(o1.z); wi[3] = wi[3] + B::as_f32(o1.w);
-      U4 n0, n1;
-      n0.x = B::as_u32(wr[0]); n0.y = B::as_u32(wi[0]); n0.z = B::as_u32(wr[1]); n0.w = B::as_u32(wi[1]);
-      n1.x = B::as_u32(wr[2]); n1.y = B::as_u32(wi[2]); n1.z = B::as_u32(wr[3]); n1.w = B::as_u32(wi[3]);
-      B::g_w128(slab, idx, n0, B::ptrue());
-      B::g_w128(slab, idx + 1, n1, B::ptrue());
-    }
-  }
   // W (+)= Zd * conj(Zv), Zv given as (re,im)-interleaved dtype pairs (KfRegs layout)
   static FFC_FN void w_accum_z(float* slab, int tau, bool first, const typename BD::KfRegs& zv, const A16& re, const A16& im) {
     const i32 lane = B::opaque(B::lane());
@@ -528,6 +483,7 @@ struct Modes : Body<B, GEO, DT> {
       B::g_w128(slab, idx + 1, n1, B::ptrue());
     }
   }
+  // zeroes a tile of the slab (only reached from the zero-trip loops of dkf / bwd, see there)
   static FFC_FN void w_zero(float* slab, int tau) {
     const i32 lane = B::opaque(B::lane());
     const i32 c = lane & 31, hi = lane >> 5;
@@ -543,9 +499,8 @@ struct Modes : Body<B, GEO, DT> {
   // per lane = 128 registers, which live in the accumulation half (AGPRs a0..a127) of the unified register
   // file, addressed explicitly by the backend (agpr_get / agpr_set).  They are invisible to the register
   // allocator, which keeps the architectural half (128 VGPRs) for the transforms; the slab is written once
-  // per chunk instead of read-modified-written for every pair.  FFC_WREG=0 selects the slab path.
+  // per chunk instead of read-modified-written for every pair.
   using F2 = typename B::F2;       // fp32 pair = one packed-math register pair
-  static constexpr int WREG = FFC_WREG < GEO::TPW ? 0 : GEO::TPW;
   struct WAcc { int unused; };
   template <int I0, int N>
   static FFC_FN void w_acc_zero_range() {
@@ -553,7 +508,8 @@ struct Modes : Body<B, GEO, DT> {
     else { w_acc_zero_range<I0, N / 2>(); w_acc_zero_range<I0 + N / 2, N - N / 2>(); }
   }
   static FFC_FN void w_acc_zero(WAcc&) {
-    if constexpr (WREG > 0) { B::agpr_reserve(); w_acc_zero_range<0, 32 * WREG>(); }
+    B::agpr_reserve();
+    w_acc_zero_range<0, 32 * GEO::TPW>();
   }
   // accumulator a[32T + 16*part + r]: part 0 = re, 1 = im, r = accumulator row slot
   template <int T, int RQ>
@@ -580,60 +536,11 @@ struct Modes : Body<B, GEO, DT> {
       }
     }
   }
-  // Round 6 experiment (FFC_WACC_MFMA = 1; measured, NOT adopted: profiles/r06_ab_wacc_mfma.txt): the sums accumulated by the MATRIX pipe.
-  // The fp32 products P = D (x) conj Z of a tile are rounded to bf16 MFMA operands (to_op form: operand dword d of K-step ms =
-  // pack(P[8 ms + 2 d], P[8 ms + 2 d + 1]), whose contraction slot (ms, lane half, e) carries accumulator row kslot_row(ms, hi, e),
-  // ffc_layout.h) and multiplied by a permuted identity straight into a[32 T ..]: W += I x P, exact fp32 accumulation of bf16-rounded
-  // products.  It removes the 128 v_accvgpr_read / _write + 16 packed adds per tile and pair of the VALU form for 16 v_cvt_pk + ~25 VALU
-  // (identity operands) + 4 MFMAs -- about 350 issue cycles per tile on the r03 cost table -- and the backward kernels run EXACTLY as
-  // fast as before (config 2: 0.6222 / 0.6236 / 0.6207 against 0.6199 / 0.6081 / 0.6236 ms, same box, interleaved; fft 4096 5 % slower):
-  // the accumulation is not on the critical path of the pair loop.  Parity-green on the simulator (209 cases) and the GPU.  Default 0.
-#ifndef FFC_WACC_MFMA
-#define FFC_WACC_MFMA 0
-#endif
-  // A operand of the identity K-step ms: lane (i = lane & 31, hi' = lane >> 5), slot e: 1.0 iff i == kslot_row(ms, hi', e)
-  static FFC_FN W4 ident_op(int ms) {
-    const i32 lane = B::opaque(B::lane());
-    const i32 t = (lane & 31) - (lane >> 5) * 4 - 16 * ms;      // = 8 (e >> 2) + (e & 3) for the matching slot, if any
-    const pred ok = (t >= 0) && ((t & 4) < 1) && (t < 12);
-    const i32 e = (t & 3) + ((t >> 3) << 2);
-    const u32 one = B::sel((e & 1) >= 1, B::uconst(0x3F800000u), B::uconst(0x00003F80u));
-    W4 w;
-#pragma unroll
-    for (int d = 0; d < 4; d++) w[d] = B::sel(ok && ((e >> 1) < d + 1) && ((e >> 1) >= d), one, B::uconst(0));
-    return w;
-  }
-  // products of accumulator rows 4 RQ .. 4 RQ + 3 with the conjugated spectrum quad z -> two operand dwords per component
-  static FFC_FN void w_prod_quarter(int RQ, const U4& z, const A16& re, const A16& im, u32 (&pr)[2], u32 (&pi)[2]) {
-    u32 wv[4] = {z.x, z.y, z.z, z.w};
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-      const int r0 = 4 * RQ + 2 * j;
-      f32 zr0 = B::template unpack_lo<DT>(wv[2 * j]), zi0 = B::template unpack_hi<DT>(wv[2 * j]);
-      f32 zr1 = B::template unpack_lo<DT>(wv[2 * j + 1]), zi1 = B::template unpack_hi<DT>(wv[2 * j + 1]);
-      f32 p0 = re[r0] * zr0 + im[r0] * zi0, p1 = re[r0 + 1] * zr1 + im[r0 + 1] * zi1;
-      f32 q0 = im[r0] * zr0 - re[r0] * zi0, q1 = im[r0 + 1] * zr1 - re[r0 + 1] * zi1;
-      pr[j] = B::template pack<DT_BF16>(p0, p1);
-      pi[j] = B::template pack<DT_BF16>(q0, q1);
-    }
-  }
+  // (round 6 measured the sums accumulated by the matrix pipe instead -- the products rounded to bf16 operands and multiplied by a permuted
+  // identity straight into a[32 T ..]: config 2 0.6222 / 0.6236 / 0.6207 against 0.6199 / 0.6081 / 0.6236 ms, same box, interleaved; fft 4096 5 %
+  // slower: the accumulation is not on the critical path of the pair loop.  profiles/r06_ab_wacc_mfma.txt; removed)
   template <int T>
   static FFC_FN void w_acc_tile(const typename BD::KfRegs& zv, const A16& re, const A16& im) {
-#if defined(FFC_KO) && (FFC_KO & 128)
-    return;        // knock-out timing experiment: no dk_f accumulation
-#endif
-    if constexpr (FFC_WACC_MFMA != 0) {
-#pragma unroll
-      for (int ms = 0; ms < 2; ms++) {
-        u32 r01[2], i01[2], r23[2], i23[2];
-        w_prod_quarter(2 * ms, zv.v[2 * ms], re, im, r01, i01);
-        w_prod_quarter(2 * ms + 1, zv.v[2 * ms + 1], re, im, r23, i23);
-        const W4 id = ident_op(ms);
-        B::template mfma_acc_bf16<32 * T>(id, B::w4(r01[0], r01[1], r23[0], r23[1]));
-        B::template mfma_acc_bf16<32 * T + 16>(id, B::w4(i01[0], i01[1], i23[0], i23[1]));
-      }
-      return;
-    }
     w_acc_quarter<T, 0>(zv.v[0], re, im);
     w_acc_quarter<T, 1>(zv.v[1], re, im);
     w_acc_quarter<T, 2>(zv.v[2], re, im);
@@ -657,12 +564,10 @@ struct Modes : Body<B, GEO, DT> {
     w_acc_store_q<T, 2>(slab, tau0, hi, c); w_acc_store_q<T, 3>(slab, tau0, hi, c);
   }
   static FFC_FN void w_acc_store(float* slab, int tau0, const WAcc&) {
-    if constexpr (WREG > 0) {
-      const i32 lane = B::opaque(B::lane());
-      const i32 c = lane & 31, hi = lane >> 5;
-      w_acc_store_t<0>(slab, tau0, hi, c); w_acc_store_t<1>(slab, tau0, hi, c);
-      w_acc_store_t<2>(slab, tau0, hi, c); w_acc_store_t<3>(slab, tau0, hi, c);
-    }
+    const i32 lane = B::opaque(B::lane());
+    const i32 c = lane & 31, hi = lane >> 5;
+    w_acc_store_t<0>(slab, tau0, hi, c); w_acc_store_t<1>(slab, tau0, hi, c);
+    w_acc_store_t<2>(slab, tau0, hi, c); w_acc_store_t<3>(slab, tau0, hi, c);
   }
   // Cross-unit reduction of the accumulation registers (UPW > 1: the UPW units of a workgroup are UPW pairs of the
   // SAME head, each with its own W in a0..a127).  Per tile: every wave parks its 32 accumulators in the (now idle)
@@ -706,7 +611,6 @@ struct Modes : Body<B, GEO, DT> {
     if constexpr (GEO::UPW == 1) {
       w_acc_store(slab, un.wq * GEO::TPW, W);
     } else {
-      static_assert(WREG == GEO::TPW, "the per-pair slab path (FFC_WREG=0) only exists for one unit per workgroup");
       static_assert(GEO::UPW * GEO::NW * 8192 <= GEO::UPW * GEO::EBYTES, "parking area fits the exchange buffers");
       const i32 lane = B::opaque(B::lane());
       B::barrier();
@@ -747,7 +651,7 @@ struct Modes : Body<B, GEO, DT> {
     BD::template tile_inv<false>(d.c.s_inv, un.wq * GEO::TPW + T, R, un, re, im);
   }
   static FFC_FN void dk_tail(const DkfArgs& d, int h, int wq) {
-    static_assert(GEO::UPW == 1 && WREG == GEO::TPW && GEO::TPW == 4, "dk tail: one unit per workgroup, sums in registers");
+    static_assert(GEO::UPW == 1 && GEO::TPW == 4, "dk tail: one unit per workgroup, sums in registers");
     const Unit un = unit_of(0, wq);
     B::barrier();              // the last pair's output rows have left the exchange buffer
     InnerRegs R;
@@ -770,7 +674,7 @@ struct Modes : Body<B, GEO, DT> {
     BD::template tile_inv<false, true>(d.c.s_inv, un.wq * GEO::TPW + T, R, un, re, im, 0, ps);
   }
   static FFC_FN void dk_tail_rp(const DkfArgs& d, int h, int wq, Pass ps) {
-    static_assert(GEO::UPW == 1 && WREG == GEO::TPW && GEO::TPW == 4 && DT == DT_BF16, "dk tail of a pass: one unit per workgroup, bf16 tables");
+    static_assert(GEO::UPW == 1 && GEO::TPW == 4 && DT == DT_BF16, "dk tail of a pass: one unit per workgroup, bf16 tables");
     const Unit un = unit_of(0, wq);
     B::barrier();              // the last pair's output rows have left the exchange buffer
     InnerRegs R;
@@ -811,7 +715,7 @@ struct Modes : Body<B, GEO, DT> {
     B::barrier();
   }
   static FFC_FN void dk_tail_multi(const DkfArgs& d, int h, int u, int wq) {
-    static_assert(GEO::UPW > 1 && WREG == GEO::TPW && GEO::TPW == 4, "dk tail: sums in registers");
+    static_assert(GEO::UPW > 1 && GEO::TPW == 4, "dk tail: sums in registers");
     const Unit un = unit_of(u, wq);
     const i32 lane = B::opaque(B::lane());
     B::barrier();              // every unit's last output rows have left the exchange buffers
@@ -835,9 +739,10 @@ struct Modes : Body<B, GEO, DT> {
   template <bool WITH_DX, bool RP = false, bool ZSAVED = false>
   static FFC_FN void bwd_tiles(const ConvArgs& a, int h, Unit un, const InnerRegs& R, const void* zs, float* slab, bool first, WAcc& W,
                                Pass ps = Pass(), bool z_stream = false, bool second = false) {
+    static_assert(GEO::TPW == 4, "one accumulator block a[32 T ..] per tile slot of the wave");
     // folded outer twiddle (Body::tile_fwd / tile_inv <.., FOLD>): the saved-spectra backward of single-pass fft 32768, whose phase A ran
     // without the twiddle (Modes::bwd)
-    constexpr bool FOLD = BD::CAN_FOLD && GEO::N1 == 32 && WITH_DX && !RP && ZSAVED && (WREG >= GEO::TPW);
+    constexpr bool FOLD = BD::CAN_FOLD && GEO::N1 == 32 && WITH_DX && !RP && ZSAVED;
     const uint8_t* fold = FOLD ? a.tab + a.t.fold : nullptr;
     typename BD::KfRegs zv;
     // FOLD: every matrix is requested one stage ahead of its use; the next tile's first matrix behind this tile's last stage (16 loop-carried registers)
@@ -846,31 +751,21 @@ struct Modes : Body<B, GEO, DT> {
 #pragma unroll 1
     for (int tt = 0; tt < GEO::TPW; tt++) {
       const int tau = un.wq * GEO::TPW + tt;
-#if !defined(FFC_NO_PRIO)
       if constexpr (WITH_DX && GEO::NW > 1) {        // second half of the tile loop: the wave that is behind outranks its partner (bwd)
         if (tt == GEO::TPW / 2) { if (second) B::template setprio<2>(); else B::template setprio<1>(); }
       }
-#endif
       z_load(zs, tau, zv, z_stream || (a.flags & 4) != 0);
       typename BD::KfRegs kf;
       constexpr bool KFL = FOLD;      // (folded-twiddle variant: the k_f tile requested behind the transform, its matrices take the registers)
       if constexpr (WITH_DX && !KFL) BD::load_kf(a, h, tau, kf);
       A16 re, im;
-      if (WREG >= GEO::TPW || tt < WREG) {
-        BD::template tile_fwd<false, false, FOLD>(tau, R, un, re, im, nullptr, fold, FOLD ? &fa : nullptr);
-        if constexpr (WITH_DX && KFL) BD::load_kf(a, h, tau, kf);
-        switch (tt) {
-          case 0: if constexpr (WREG > 0) w_acc_tile<0>(zv, re, im); break;
-          case 1: if constexpr (WREG > 1) w_acc_tile<1>(zv, re, im); break;
-          case 2: if constexpr (WREG > 2) w_acc_tile<2>(zv, re, im); break;
-          default: if constexpr (WREG > 3) w_acc_tile<3>(zv, re, im); break;
-        }
-      } else {
-        WOld wold;
-        w_load_old(slab, tau, first, wold);
-        BD::template tile_fwd<false>(tau, R, un, re, im);
-        if constexpr (WITH_DX && KFL) BD::load_kf(a, h, tau, kf);
-        w_update(slab, tau, wold, zv, re, im);
+      BD::template tile_fwd<false, false, FOLD>(tau, R, un, re, im, nullptr, fold, FOLD ? &fa : nullptr);
+      if constexpr (WITH_DX && KFL) BD::load_kf(a, h, tau, kf);
+      switch (tt) {
+        case 0: w_acc_tile<0>(zv, re, im); break;
+        case 1: w_acc_tile<1>(zv, re, im); break;
+        case 2: w_acc_tile<2>(zv, re, im); break;
+        default: w_acc_tile<3>(zv, re, im); break;
       }
       if constexpr (WITH_DX) {
         typename BD::Mat2 g[2];
@@ -949,8 +844,10 @@ struct Modes : Body<B, GEO, DT> {
           BD::template load_inner<false>(R, un);
           bwd_tiles<false, RP>(a, h, un, R, zs, slab, it == 0, W, ps);
         } else if (it == 0) {
+          // (zero trips: every tile's sums live in registers.  Left in place because the compiler allocates the backward kernels' registers
+          // differently without this branch; taking it out needs a same-box timing run of its own)
 #pragma unroll 1
-          for (int tt = WREG; tt < GEO::TPW; tt++) w_zero(slab, un.wq * GEO::TPW + tt);
+          for (int tt = GEO::TPW; tt < GEO::TPW; tt++) w_zero(slab, un.wq * GEO::TPW + tt);
         }
         BD::unit_barrier();
       }
@@ -966,8 +863,7 @@ struct Modes : Body<B, GEO, DT> {
         for (int k0 = 0; k0 < a.R; k0++) {
           Pass ps; ps.k0 = k0; ps.R = a.R;
           InnerPass ip;
-          if constexpr (FFC_IP_LEAN != 0) BD::load_inner_pass_lean(ip, k0);     // round 6: matrices / twiddles of the pass from LDS at their use
-          else BD::load_inner_pass(ip, k0);
+          BD::load_inner_pass_lean(ip, k0);     // round 6: matrices / twiddles of the pass from LDS at their use
           A16 wre = B::a16_zero(), wim = B::a16_zero();
 #pragma unroll 1
           for (int it = 0; it < iters; it++) {
@@ -977,12 +873,12 @@ struct Modes : Body<B, GEO, DT> {
               A16 re, im;
               BD::template rows_in_rp<BD::NCH>(av, h, q, un, ps);
               B::lds_fence();
-              BD::template tile_fwd<true, true, false, FFC_IP_LEAN != 0>(0, R, un, re, im, &ip);
+              BD::template tile_fwd<true, true, false, true>(0, R, un, re, im, &ip);
               z_pack(re, im, zv);
               B::lds_fence();
               BD::template rows_in_rp<BD::NCH>(ad, h, q, un, ps);
               B::lds_fence();
-              BD::template tile_fwd<true, true, false, FFC_IP_LEAN != 0>(0, R, un, re, im, &ip);
+              BD::template tile_fwd<true, true, false, true>(0, R, un, re, im, &ip);
               w_add(wre, wim, zv, re, im);
               B::lds_fence();
             }
@@ -1112,20 +1008,13 @@ struct Modes : Body<B, GEO, DT> {
       uint8_t* zs = (uint8_t*)d.zscratch + ((int64_t)(wg_linear * GEO::UPW + u)) * (GEO::N * 4);
       WAcc W;
       w_acc_zero(W);
-      // profiling build (-DFFC_BWD_PROF, lib/variants): s_memtime sums per phase, [wg][wave][16] in a.prof
-#if defined(FFC_BWD_PROF)
-      unsigned long long pacc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, pt0 = 0, pt1 = 0;
-#define FFC_BTICK(k) if constexpr (!RP) { pt1 = B::clock(); pacc[k] += pt1 - pt0; pt0 = pt1; }
-#else
-#define FFC_BTICK(k)
-#endif
       // (round 3: requesting the next rows ahead of the store bursts -- the next pair's u rows before rows_out, the dout rows
       // before the last scratch store -- needs 32 live registers at points where the allocator, which treats a0..a127 as free
       // space, parks them in the accumulation registers; warm-up loads into 4 registers did not shorten the wait either:
       // DESIGN.md section 7)
       const bool have_z = ZM < 0 ? d.zin != nullptr : ZM == 1;
       // FFC_FOLD_TW: the saved-spectra kernel of single-pass fft 32768 runs phase A of dout without the outer twiddle (bwd_tiles folds it)
-      constexpr bool FOLDZ = BD::CAN_FOLD && GEO::N1 == 32 && ZM == 1 && !RP && (WREG >= GEO::TPW);
+      constexpr bool FOLDZ = BD::CAN_FOLD && GEO::N1 == 32 && ZM == 1 && !RP;
       // input rows of dout by LDS-DMA into the dead half of the exchange buffer (Body::rows_dma): saved-spectra form of the
       // HALF kernels with a 32-point outer digit, plain rows (no gate multiply / side product on the way in), 16-byte-aligned
       // tensors; tuning flag 8 (FFC_FLAGS) keeps the register path for A/B runs
@@ -1135,18 +1024,11 @@ struct Modes : Body<B, GEO, DT> {
       // wave priority by progress between two barriers (Body::outer_jobs has the measurements): row loads 1, phase A 0, the
       // tile loops 3 then 1 (2 for the second-dispatched wave of the SIMD), phase C 3, stores 2
       const bool second = wv >= 4;
-#if defined(FFC_NO_PRIO)
-#define FFC_BPRIO(x)
-#else
 #define FFC_BPRIO(x) if constexpr (GEO::NW > 1) B::template setprio<x>();
-#endif
 #pragma unroll 1
       for (int it = 0; it < iters; it++) {
         const int p = p0 + it * GEO::UPW + u;
         const bool act = p < p1;
-#if defined(FFC_BWD_PROF)
-        if constexpr (!RP) pt0 = B::clock();
-#endif
         FFC_BPRIO(1)
         // saved spectra (d.zin): the pair's first transform is skipped, its spectrum is read from the forward pass's copy
         const void* zp = !have_z ? (const void*)zs
@@ -1162,7 +1044,7 @@ struct Modes : Body<B, GEO, DT> {
               for (int tt = 0; tt < GEO::TPW; tt++) {
                 const int tau = un.wq * GEO::TPW + tt;
                 typename BD::KfRegs zv, kf;
-                z_load(zp, tau, zv, FFC_Z_STREAM);
+                z_load(zp, tau, zv, BD::Z_STREAM);
                 BD::load_kf(a, hk, tau, kf);
                 A16 re, im;
                 z_unpack(zv, re, im);
@@ -1178,13 +1060,11 @@ struct Modes : Body<B, GEO, DT> {
               else BD::template rows_out<NCX>(aq, h, p, un);
             }
           }
-          FFC_BTICK(5)
           if (act) {
             bool done = false;
             if constexpr (DMA_OK) {
               if (dma) {      // the rows were requested behind the previous pair's phase C (or in the prologue)
                 BD::rows_dma_finish(ad, p, un);
-                FFC_BTICK(6)
                 FFC_BPRIO(0)
                 BD::template outer_stage<true, HALF, RP, true, FOLDZ>(a.L, un, a.s_fwd, ps);
                 done = true;
@@ -1194,24 +1074,19 @@ struct Modes : Body<B, GEO, DT> {
               if constexpr (RP) BD::template rows_in_rp<NCX>(ad, h, p, un, ps);
               else BD::template rows_in<NCX>(ad, h, p, un);
               B::lds_fence();
-              FFC_BTICK(6)
               FFC_BPRIO(0)
               BD::template outer_stage<true, HALF, RP, false, FOLDZ>(a.L, un, a.s_fwd, ps);
             }
-            FFC_BTICK(7)
           }
         } else {
           if (act) {
             if constexpr (RP) BD::template rows_in_rp<NCX>(av, h, p, un, ps);
             else BD::template rows_in<NCX>(av, h, p, un);
             B::lds_fence();
-            FFC_BTICK(0)
             FFC_BPRIO(0)
             BD::template outer_stage<true, HALF, RP>(a.L, un, a.s_fwd, ps);
-            FFC_BTICK(1)
           }
           BD::unit_barrier();
-          FFC_BTICK(2)
           FFC_BPRIO(3)
           if (act) {
             BD::template load_inner<false>(R, un);
@@ -1230,9 +1105,7 @@ struct Modes : Body<B, GEO, DT> {
               }
             }
           }
-          FFC_BTICK(3)
           BD::unit_barrier();
-          FFC_BTICK(4)
           FFC_BPRIO(1)
           if (dpost_tf) {
             if (act) {
@@ -1244,35 +1117,30 @@ struct Modes : Body<B, GEO, DT> {
             // no barrier: phase C, rows_out and the rows_in / phase A that follow all stay inside the wave's own
             // column slice of E (same as between two pairs of the forward kernel)
           }
-          FFC_BTICK(5)
           if (act) {
             if constexpr (RP) BD::template rows_in_rp<NCX>(ad, h, p, un, ps);
             else BD::template rows_in<NCX>(ad, h, p, un);
             B::lds_fence();
-            FFC_BTICK(6)
             FFC_BPRIO(0)
             BD::template outer_stage<true, HALF, RP>(a.L, un, a.s_fwd, ps);
-            FFC_BTICK(7)
           }
         }
         BD::unit_barrier();
-        FFC_BTICK(8)
         FFC_BPRIO(3)
         if (act) {
           BD::template load_inner<false>(R, un);
-          bwd_tiles<true, RP, ZM == 1>(a, hk, un, R, zp, slab, it == 0, W, ps, have_z && FFC_Z_STREAM, second);
+          bwd_tiles<true, RP, ZM == 1>(a, hk, un, R, zp, slab, it == 0, W, ps, have_z && BD::Z_STREAM, second);
         } else if (it == 0) {
+          // (zero trips: every tile's sums live in registers.  Left in place because the compiler allocates the backward kernels' registers
+          // differently without this branch; taking it out needs a same-box timing run of its own)
 #pragma unroll 1
-          for (int tt = WREG; tt < GEO::TPW; tt++) w_zero(slab, un.wq * GEO::TPW + tt);
+          for (int tt = GEO::TPW; tt < GEO::TPW; tt++) w_zero(slab, un.wq * GEO::TPW + tt);
         }
-        FFC_BTICK(9)
         BD::unit_barrier();
-        FFC_BTICK(10)
         FFC_BPRIO(3)
         if (act) {
           BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps);
           B::lds_fence();
-          FFC_BTICK(11)
           // the next pair's dout rows into E rows 16.. (dead: phase C has read them), in flight under the du stores below
           if constexpr (DMA_OK) { if (dma && p + GEO::UPW < p1) BD::rows_dma(ad, h, p + GEO::UPW, un); }
           FFC_BPRIO(2)
@@ -1283,22 +1151,12 @@ struct Modes : Body<B, GEO, DT> {
             BD::template rows_out<NCX>(ao, h, p, un);
             if (d.dpre) BD::template rows_out<NCX>(ap, h, p, un);
           }
-          FFC_BTICK(12)
         }
       }
-#if defined(FFC_BWD_PROF)
-      if (!RP && a.prof) {
-        const i32 lane = B::lane();
-        unsigned long long* dst = a.prof + ((long long)wg_linear * GEO::WGW + wv) * 16;
-#pragma unroll
-        for (int k = 0; k < 16; k++) B::g_w64(dst, lane * 0 + k, B::u2_from64(pacc[k]), lane < 1);
-      }
-#endif
-#undef FFC_BTICK
 #undef FFC_BPRIO
       // (not the one-wave-per-unit kernel of fft 4096: with the tail its register allocation overflows into the accumulation
       // registers, build.py check_agpr)
-      if constexpr (!RP && WREG == GEO::TPW && GEO::NW > 1) {
+      if constexpr (!RP && GEO::NW > 1) {
         if (d.dk_out || d.dk_pair) {      // dk straight from the accumulation registers (nchunk == 1)
           using MB = Modes<B, GEO, DT_BF16>;       // the dk inverse always runs in bf16 operand arithmetic
           if constexpr (DT != DT_BF16) {           // fp16 plan: swap the plan's bf16 tables into LDS first
@@ -1310,7 +1168,7 @@ struct Modes : Body<B, GEO, DT> {
           return;
         }
       }
-      if constexpr (RP && WREG == GEO::TPW && GEO::NW > 1 && GEO::UPW == 1 && DT == DT_BF16) {
+      if constexpr (RP && GEO::NW > 1 && GEO::UPW == 1 && DT == DT_BF16) {
         if (d.dk_out) { dk_tail_rp(d, h, un.wq, ps); return; }      // this pass's share of dk from the accumulation registers (nchunk == 1)
       }
       w_acc_finish(slab, u, un, W);
@@ -1328,8 +1186,7 @@ struct Modes : Body<B, GEO, DT> {
           // round 6: the pass's two matrices and its twiddle table are read from LDS where they are used (tile_fwd / tile_inv <.., IPL>); with all
           // 80 registers of a pass resident next to the dk_f sums this kernel spilled 34 - 43 registers into scratch memory inside the pair loop
           // (fft 2048 backward 0.084 -> 0.062 ms at B16 H768, profiles/r06_ab_fft2048.txt)
-          if constexpr (FFC_IP_LEAN != 0) BD::load_inner_pass_lean(ip, k0);
-          else BD::load_inner_pass(ip, k0);
+          BD::load_inner_pass_lean(ip, k0);
           A16 wre = B::a16_zero(), wim = B::a16_zero();
 #pragma unroll 1
           for (int it = 0; it < iters; it++) {
@@ -1341,23 +1198,23 @@ struct Modes : Body<B, GEO, DT> {
               BD::load_kf(a, h * a.R + k0, 0, kf);
               typename BD::KfRegs zk;
               if (d.zin) {       // spectrum saved by the forward pass: the tile's first transform is skipped
-                z_load(BD::z_slot_small(const_cast<void*>(d.zin), h, a.npair, q, a.R, k0), 0, zk, FFC_Z_STREAM);
+                z_load(BD::z_slot_small(const_cast<void*>(d.zin), h, a.npair, q, a.R, k0), 0, zk, BD::Z_STREAM);
               } else {
                 BD::template rows_in_rp<BD::NCH>(av, h, q, un, ps);
                 B::lds_fence();
-                BD::template tile_fwd<true, true, false, FFC_IP_LEAN != 0>(0, R, un, re, im, &ip);
+                BD::template tile_fwd<true, true, false, true>(0, R, un, re, im, &ip);
                 z_pack(re, im, zv);
                 B::lds_fence();
               }
               if (ad.aux_in && k0 == 0) BD::template rows_aux_rp<BD::NCH>(ad, h, q, un);      // dpost = dout * yraw, once per pair
               BD::template rows_in_rp<BD::NCH>(ad, h, q, un, ps);
               B::lds_fence();
-              BD::template tile_fwd<true, true, false, FFC_IP_LEAN != 0>(0, R, un, re, im, &ip);
+              BD::template tile_fwd<true, true, false, true>(0, R, un, re, im, &ip);
               if (d.zin) w_add_k(wre, wim, zk, re, im);
               else w_add(wre, wim, zv, re, im);
               kf_conj_mul(kf, re, im);
               B::lds_fence();
-              BD::template tile_inv<true, false, true, false, FFC_IP_LEAN != 0>(a.s_inv, 0, R, un, re, im, 0, Pass(), &ip);
+              BD::template tile_inv<true, false, true, false, true>(a.s_inv, 0, R, un, re, im, 0, Pass(), &ip);
               B::lds_fence();
               BD::template rows_out_rp<BD::NCH>(ao, h, q, un, ps);
               if (d.dpre) BD::template rows_out_rp<BD::NCH>(ap, h, q, un, ps);
@@ -1382,7 +1239,7 @@ struct Modes : Body<B, GEO, DT> {
           BD::load_kf(a, h, 0, kf);
           typename BD::KfRegs zk;
           if (d.zin) {       // spectrum saved by the forward pass: the tile's first transform is skipped
-            z_load(BD::z_slot_small(const_cast<void*>(d.zin), h, a.npair, q, 1, 0), 0, zk, FFC_Z_STREAM);
+            z_load(BD::z_slot_small(const_cast<void*>(d.zin), h, a.npair, q, 1, 0), 0, zk, BD::Z_STREAM);
           } else {
             BD::rows_in(av, h, q, un);
             B::lds_fence();
@@ -1677,7 +1534,7 @@ struct Modes : Body<B, GEO, DT> {
             BD::load_inner_pass(ip, k0);
             A16 re, im;
             w_load(a, unit_id * a.R + k0, 0, re, im, a.R);
-            BD::template tile_inv<true, false, true, false, FFC_IP_LEAN != 0>(a.s_inv, 0, R, un, re, im, 0, Pass(), &ip);
+            BD::template tile_inv<true, false, true, false, true>(a.s_inv, 0, R, un, re, im, 0, Pass(), &ip);
             B::lds_fence();
             dk_rows_out_rp(a, unit_id, un, ps);
             B::lds_fence();

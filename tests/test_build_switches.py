@@ -178,3 +178,33 @@ def test_per_element_twiddle_variant_matches_the_oracle(tmp_path):
                 assert rel(b, want) < 1.5e-2, f"{what}: default build against the oracle {rel(b, want):.3e}"
                 assert rel(a, want) < 1.5e-2, f"{what}: FFC_BIG_CHAIN=0 against the oracle {rel(a, want):.3e}"
                 assert rel(a, b.astype(np.float64)) < 1e-2, f"{what}: FFC_BIG_CHAIN=0 against the default build {rel(a, b.astype(np.float64)):.3e}"
+
+
+# ---------------------------------------------------------------- the rule of the code base: a compile-time switch exists only if a test builds its other form
+def test_every_switch_is_documented():
+    """The names introduced as `#ifndef FFC_X` / `#define FFC_X` in csrc/ are exactly the first column of the switch table of DESIGN.md section 7
+    (each row there names the test that builds the switch's other form), and no name of the table's "removed" row is left in csrc/ or build.py."""
+    import glob, re
+    csrc = os.path.join(PKG, "csrc")
+    files = [f for pat in ("*.h", "*.hip", "*.cpp") for f in glob.glob(os.path.join(csrc, pat))]
+    text = {f: open(f).read() for f in files}
+    defined = {m.group(1) for t in text.values() for m in re.finditer(r"^[ \t]*#[ \t]*ifndef[ \t]+(FFC_\w+)[^\n]*\n[ \t]*#[ \t]*define[ \t]+\1\b", t, re.M)}
+    defined.discard("FFC_FN")
+    design = open(os.path.join(os.path.dirname(HERE), "DESIGN.md")).read()
+    sec = design[design.index("## 7. Build switches"):]
+    rows = [l for l in sec[:sec.index("\n## 8.")].splitlines() if l.startswith("|")]
+    assert rows[0].startswith("| switch |") and rows[1].startswith("|---"), rows[:2]
+    documented, removed = set(), set()
+    for row in rows[2:]:
+        cell = row.split("|")[1]
+        if cell.strip().startswith("(removed"):
+            removed |= set(re.findall(r"`(FFC_\w+)`", cell))
+            continue
+        names = re.findall(r"`(\w+)`", cell)       # `FFC_X` (`_A`, `_B`) stands for FFC_X, FFC_X_A, FFC_X_B
+        assert names and names[0].startswith("FFC_"), row
+        documented |= {names[0]} | {names[0] + n for n in names[1:] if n.startswith("_")} | {n for n in names[1:] if n.startswith("FFC_")}
+    assert defined == documented, (sorted(defined - documented), sorted(documented - defined))
+    assert removed and not (removed & documented)
+    text[os.path.join(PKG, "build.py")] = open(os.path.join(PKG, "build.py")).read()
+    left = sorted((n, os.path.basename(f)) for f, t in text.items() for n in removed if re.search(r"\b%s\b" % n, t))
+    assert not left, left
