@@ -24,6 +24,8 @@ class _ConvCache(torch.nn.Module):
         self._convs = {}
 
     def _conv_for(self, x, keep=None):
+        if not torch.is_tensor(x) or x.dtype not in (torch.bfloat16, torch.float16):
+            raise RuntimeError(f"{type(self).__name__}: x must be a bf16 / fp16 tensor, got {getattr(x, 'dtype', type(x))}")
         key = (2 * x.shape[-1], x.dtype)
         conv = self._convs.get(key)
         if conv is None:

@@ -169,13 +169,17 @@ def test_big_sizes_through_outer_levels(N, L, B, gated):
     assert rel(dk, dkref) < 1.5e-2
 
 
-@pytest.mark.parametrize("N,L,rows", [(32768, 16384, 4), (32768, 32768, 2), (16384, 8192, 4), (16384, 5000, 1)])
-def test_frequency_sparse_kernel_skips_zero_rows(N, L, rows):
+SP_CASES = [(32768, 16384, 4), (32768, 32768, 2), (16384, 8192, 4), (16384, 5000, 1), (16384, 8192, 3)]      # N, L, rows
+
+
+@pytest.mark.parametrize("N,L,rows,dt", [pytest.param(*c, dt, id="-".join(str(v) for v in c) + ("-fp16" if dt else "")) for c in SP_CASES for dt in (0, 1)])
+def test_frequency_sparse_kernel_skips_zero_rows(N, L, rows, dt):
     """ffc_conv_fwd_sparse (kernel variant SP): with a low-pass k_f (non-zero bins |f| < rows N / 32) the compute-skipping
     kernel returns bit for bit what the dense kernel returns on the same masked k_f, forward and conj(k_f) pass (fft 16384: to
-    rounding, the dense kernel there folds its outer twiddle)."""
+    rounding, the dense kernel there folds its outer twiddle; fft 32768 in fp16: all but 2^-6 of the elements, the order of the
+    fp32 sums differs).  Both dtypes; every row count 1 .. 4 the product hands it."""
     rng = np.random.default_rng(N + rows)
-    dt, B, H = 0, 3, 1
+    B, H = 3, 1
     u, g1, g2 = (rng.standard_normal((B, H, L)).astype(np.float32) for _ in range(3))
     k = (rng.standard_normal((H, L)) * 0.1).astype(np.float32)
     kfn = np.fft.fft(k.astype(np.float64), n=N)
@@ -192,6 +196,16 @@ def test_frequency_sparse_kernel_skips_zero_rows(N, L, rows):
             S.lib().ffcsim_set_sparse(0)
         if N == 16384:      # round 5: the dense forward of fft 16384 folds its outer twiddle into the stage matrices, the sparse variant keeps the chains
             assert rel(S.from_bits(sparse, dt), S.from_bits(dense, dt).astype(np.float64)) < 1e-2
+        elif dt == 1:
+            # fp16: the sparse inverse stage sums its 8 live rows in ONE K-step, the dense one in two among 24 zero rows.  Products of fp16 operands have
+            # 22 significant bits, so their fp32 sums round and depend on that order (bf16: 16 bits, the sums stay exact -- bit for bit below).  A sum
+            # moved by c fp32 steps (2^-24; c <= 4 for 8 terms) crosses an fp16 rounding boundary (spacing 2^-11) c times in 2^13.  One such fp16 step
+            # moves the 32 sums of the next stage by 2^-11 / sqrt(32) each, 1 / sqrt(32) of them across a boundary (5.7), and again in the stage
+            # behind: 1 + 5.7 + 32 = 39 changed roundings per crossing, a fraction p <= 39 x 4 x 2^-13 < 2^-6 of the elements, each by one fp16 step:
+            # rel-L2 <= sqrt(p) 2^-11 = 6e-5 (measured: 0.2 .. 0.5 % of the elements, 2.5e-5)
+            a, b = S.from_bits(sparse, dt).astype(np.float64), S.from_bits(dense, dt).astype(np.float64)
+            assert (sparse != dense).mean() < 2.0 ** -6, f"conj={conj}: {(sparse != dense).mean():.2%} of the elements differ"
+            assert rel(a, b) < 1e-4
         else:
             assert np.array_equal(dense, sparse), f"conj={conj}: {int((dense != sparse).sum())} elements differ"
     yref = np.fft.ifft(np.fft.fft(q(u, dt).astype(np.float64) * q(g1, dt), n=N) * kfn[None], n=N).real[..., :L] * q(g2, dt)
