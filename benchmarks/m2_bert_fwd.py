@@ -7,8 +7,11 @@ use: bidirectional (the filter has 2 L taps, k = pad(k_fwd, (0, L)) + pad(flip(k
 kernel fills it), residual long convolution (y = x2 * conv(x1 * v, k) + conv(v, k2)) and inference mode (the two filters are
 parameters; :57-64).  Random weights (no network: no checkpoint).  The encoder around it is LayerNorm -> mixer -> +res ->
 LayerNorm -> GLU MLP (4x) -> +res; the reference's MLP is a block-diagonal Monarch GLU (bert_layers.py), here a dense GLU of the
-same shapes: it is not on this package's path and is the same code in all three forms.
-   fused    gated_conv_from_slices (x1 / x2 / v read in place, gates inside the kernel) + FlashFFTConv(v, k2)
+same shapes: it is not on this package's path and is the same code in all forms.
+   fused    gated_conv_from_slices(.., k, k_res = k2): conv(v, k2) reading the v slice in place, then the gated kernel (x1 / x2 / v
+            in place) with that result added in its output epilogue -- two launches, 7 row tensors of traffic per mixer
+   fused_parent  the form before the fused residual input: gated_conv_from_slices + FlashFFTConv(v.contiguous(), k2) + a torch
+            add (a copy and an add kernel more: 11 row tensors), kept so that one run shows both
    dropin   the reference caller code verbatim on this package's modules (:125-170)
    torch    nn.Conv1d + torch.fft (the non-flash mixer, monarch_mixer_sequence_mixer.py)
 Prints one JSON line per (config, form): ms per forward, tokens/ms, seqs/s (the three numbers the reference prints) and the
@@ -53,10 +56,13 @@ class SequenceMixer(nn.Module):
     def forward(self, u):
         B, L, H = u.shape
         k, k2 = self.filter.float(), self.filter2.float()
-        if self.form == "fused":      # projections as batched GEMMs on transposed views: no layout copy on either side
+        if self.form in ("fused", "fused_parent"):      # projections as batched GEMMs on transposed views: no layout copy on either side
             uc = self.short_filter(project_in(self.in_linear.weight, u))
-            y = gated_conv_from_slices(self.flashfftconv, uc, k)  # x2 * conv(x1 * v, k), slices read in place
-            y = y + self.flashfftconv(uc[:, 2 * H:].contiguous(), k2)
+            if self.form == "fused":
+                y = gated_conv_from_slices(self.flashfftconv, uc, k, k2)      # x2 * conv(x1 * v, k) + conv(v, k2), slices read in place
+            else:
+                y = gated_conv_from_slices(self.flashfftconv, uc, k)  # x2 * conv(x1 * v, k), slices read in place
+                y = y + self.flashfftconv(uc[:, 2 * H:].contiguous(), k2)
             return project_out(self.out_linear.weight, self.out_linear.bias, y)
         u = u.transpose(-1, -2)
         x1x2v = (self.in_linear.weight @ u).contiguous()          # the reference drops the in_linear bias (:124-125)
@@ -113,7 +119,7 @@ def run(name, dtype=torch.bfloat16):
     torch.manual_seed(1)
     u = torch.randn(B, L, d_model, device="cuda").to(dtype)
     outs = {}
-    for form in ("torch", "dropin", "fused"):
+    for form in ("torch", "dropin", "fused_parent", "fused"):
         torch.manual_seed(0)
         model = Encoder(d_model, n_layer, L, form, dtype).cuda().to(dtype).eval()
         with torch.no_grad():

@@ -11,7 +11,7 @@ SIM_SO = os.path.join(LIB, "libffcsim.so")
 #   addressed by hand in the backward kernels (dk_f partial sums) and must never be picked by the allocator.
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "--amdgpu-mfma-vgpr-form", "-fPIC"]
 AGPR_CHECKED = ["ffc_k_dkf.hip", "ffc_k_bwd.hip", "ffc_k_bwdz.hip"]     # translation units whose device code is scanned by check_agpr()
-HIP_SRCS = ["ffc_hip.hip", "ffc_k_conv.hip", "ffc_k_kfft.hip", "ffc_k_dkf.hip", "ffc_k_bwd.hip", "ffc_k_bwdz.hip", "ffc_k_dk.hip", "ffc_k_big.hip", "ffc_conv1d.hip", "ffc_conv1d_t0.hip", "ffc_conv1d_t1.hip", "ffc_conv1d_t2.hip", "ffc_plan.cpp"]
+HIP_SRCS = ["ffc_hip.hip", "ffc_k_conv.hip", "ffc_k_conv_res.hip", "ffc_k_kfft.hip", "ffc_k_dkf.hip", "ffc_k_bwd.hip", "ffc_k_bwdz.hip", "ffc_k_dk.hip", "ffc_k_big.hip", "ffc_conv1d.hip", "ffc_conv1d_t0.hip", "ffc_conv1d_t1.hip", "ffc_conv1d_t2.hip", "ffc_plan.cpp"]
 SIM_SRCS = ["ffc_sim.cpp", "ffc_plan.cpp"]
 
 
@@ -199,7 +199,7 @@ def build_hip(force=False, verbose=False, variant=None, extra_flags=(), srcs=Non
             return out, True
         return out, False
 
-    jobs = sorted(HIP_SRCS, key=lambda f: not (f in AGPR_CHECKED or f == "ffc_k_conv.hip" or f.startswith('ffc_conv1d_t')))   # longest first
+    jobs = sorted(HIP_SRCS, key=lambda f: not (f in AGPR_CHECKED or f in ("ffc_k_conv.hip", "ffc_k_conv_res.hip") or f.startswith('ffc_conv1d_t')))   # longest first
     with ThreadPoolExecutor(max_workers=min(10, os.cpu_count() or 4)) as ex:
         res = list(ex.map(compile_one, jobs))
     objs = [o for o, _ in res]

@@ -73,6 +73,11 @@ struct ConvArgs {
   const void* kfuse_x;     // instead of kfuse_k: complex input, pair-plane tensor (2, H, N) dtype (inner k_f rows of the HBM-level sizes)
   int kfuse_Lk, kfuse_fast;
   float kfuse_scale;       // s_k / s_fwd (KfArgs::scale; bf16 plans: prescale 1)
+  // forward only, optional (ffc_conv_fwd_res): a row tensor added in the output epilogue, y = postgate * conv(u * pregate, k) + addend
+  // (fp32 product and sum, rounded once).  Addressed like postgate / sbp; read by the kernels instantiated on a backend with HAS_ADD
+  // only (DevBA), which are only launched with it set -- every other kernel compiles no addend code.  yraw never includes it.
+  const void* addend;
+  int64_t sba;
 };
 
 // One pass of a multi-pass size (fft size N = R * M, M = GEO::N = N1 * Mi; HostPlan::R).  With n = n0 M + n1 Mi + mi and
@@ -740,15 +745,18 @@ struct Body {
 #ifndef FFC_GATE_BATCH_OUT
 #define FFC_GATE_BATCH_OUT FFC_GATE_BATCH      // (the output side holds no prefetched rows: the backward kernels afford a larger batch here)
 #endif
-  template <int NC>
+  // ADD (kernels of a HAS_ADD backend, ffc_conv_fwd_res): the addend rows' loads join the batch, y = v * gate + addend in fp32, rounded once;
+  // GATE = false (ADD only): y = v + addend, the ungated form with its addend loads batched the same way
+  template <int NC, bool ADD = false, bool GATE = true>
   static FFC_FN void rows_out_g(const ConvArgs& a, int h, int pq, Unit un) {
+    static_assert(ADD || GATE, "rows_out_g: nothing to load");
     constexpr int GB = FFC_GATE_BATCH_OUT <= 0 ? 1 : (NC < FFC_GATE_BATCH_OUT ? NC : FFC_GATE_BATCH_OUT);
     static_assert(NC % GB == 0, "gate batch");
     const i32 lane = B::opaque(B::lane());
     const int fast = a.stream ? 2 : 1;
 #pragma unroll
     for (int ib = 0; ib < NC; ib += GB) {
-      U4 G[GB][2];
+      U4 G[GB][2], Rr[GB][2];
 #pragma unroll
       for (int jj = 0; jj < GB; jj++) {
         const int i = ib + jj;
@@ -759,10 +767,12 @@ struct Body {
           if constexpr (GEO::OUTER) {
             const int b = 2 * pq + pl;
             const bool ok = b < a.B;
-            G[jj][pl] = gload8((const uint16_t*)a.postgate + row_off(b, ok, a.sbp, h, a.L), row * GEO::Mi + m, a.L, fast, ok);
+            if constexpr (GATE) G[jj][pl] = gload8((const uint16_t*)a.postgate + row_off(b, ok, a.sbp, h, a.L), row * GEO::Mi + m, a.L, fast, ok);
+            if constexpr (ADD) Rr[jj][pl] = gload8((const uint16_t*)a.addend + row_off(b, ok, a.sba, h, a.L), row * GEO::Mi + m, a.L, fast, ok);
           } else {
             i32 b = (row + pq * GEO::G) * 2 + pl;
-            G[jj][pl] = gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, fast, b < a.B);
+            if constexpr (GATE) G[jj][pl] = gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, fast, b < a.B);
+            if constexpr (ADD) Rr[jj][pl] = gload8_rows((const uint16_t*)a.addend, b, h, a, a.sba, m, fast, b < a.B);
           }
         }
       }
@@ -780,7 +790,9 @@ struct Body {
           U4 v;
           v.x = B::sel(sw, o.z, o.x); v.y = B::sel(sw, o.w, o.y);
           v.z = B::sel(sw, o.x, o.z); v.w = B::sel(sw, o.y, o.w);
-          v = mul4(v, G[jj][pl]);
+          if constexpr (ADD && GATE) v = fma4(v, G[jj][pl], Rr[jj][pl]);
+          else if constexpr (ADD) v = sum4(v, Rr[jj][pl]);
+          else v = mul4(v, G[jj][pl]);
           if constexpr (GEO::OUTER) {
             const int b = 2 * pq + pl;
             const bool ok = b < a.B;
@@ -793,10 +805,14 @@ struct Body {
       }
     }
   }
-  template <int NC = NCH>
+  // ADD: a.addend is set (the launcher runs a HAS_ADD kernel only then); ADD = false ignores it (the copy of the output before the gate, yraw)
+  template <int NC = NCH, bool ADD = B::HAS_ADD>
   static FFC_FN void rows_out(const ConvArgs& a, int h, int pq, Unit un) {
     if constexpr (FFC_GATE_BATCH > 0) {
-      if (a.fast && a.postgate) { rows_out_g<NC>(a, h, pq, un); return; }
+      if (a.fast && a.postgate) { rows_out_g<NC, ADD>(a, h, pq, un); return; }
+      if constexpr (ADD) {
+        if (a.fast) { rows_out_g<NC, true, false>(a, h, pq, un); return; }
+      }
     }
     const i32 lane = B::opaque(B::lane());
     const int fast = a.fast ? (a.stream ? 2 : 1) : 0;     // 2: streaming (non-temporal) fast path
@@ -816,7 +832,11 @@ struct Body {
           const int b = 2 * pq + pl;
           const bool ok = b < a.B;
           i32 n = row * GEO::Mi + m;
-          if (a.postgate) {
+          if constexpr (ADD) {
+            U4 r = gload8((const uint16_t*)a.addend + row_off(b, ok, a.sba, h, a.L), n, a.L, fast, ok);
+            if (a.postgate) v = fma4(v, gload8((const uint16_t*)a.postgate + row_off(b, ok, a.sbp, h, a.L), n, a.L, fast, ok), r);
+            else v = sum4(v, r);
+          } else if (a.postgate) {
             U4 g = gload8((const uint16_t*)a.postgate + row_off(b, ok, a.sbp, h, a.L), n, a.L, fast, ok);
             v.x = mul2(v.x, g.x); v.y = mul2(v.y, g.y); v.z = mul2(v.z, g.z); v.w = mul2(v.w, g.w);
           }
@@ -824,7 +844,11 @@ struct Body {
         } else {
           i32 b = (row + pq * GEO::G) * 2 + pl;
           pred ok = b < a.B;
-          if (a.postgate) {
+          if constexpr (ADD) {
+            U4 r = gload8_rows((const uint16_t*)a.addend, b, h, a, a.sba, m, fast, ok);
+            if (a.postgate) v = fma4(v, gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, fast, ok), r);
+            else v = sum4(v, r);
+          } else if (a.postgate) {
             U4 g = gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, fast, ok);
             v.x = mul2(v.x, g.x); v.y = mul2(v.y, g.y); v.z = mul2(v.z, g.z); v.w = mul2(v.w, g.w);
           }
@@ -847,6 +871,26 @@ struct Body {
   }
   static FFC_FN U4 mul4(const U4& v, const U4& g) {
     U4 o; o.x = mul2(v.x, g.x); o.y = mul2(v.y, g.y); o.z = mul2(v.z, g.z); o.w = mul2(v.w, g.w);
+    return o;
+  }
+  // v * g + r and v + r on packed dtype pairs: fp32 arithmetic, ONE rounding (the product of two 16-bit values is exact in fp32, so a
+  // fused and an unfused multiply-add agree): the output epilogue with an addend (ConvArgs::addend)
+  static FFC_FN u32 fma2(u32 v, u32 g, u32 r) {
+    f32 lo = B::template unpack_lo<DT>(v) * B::template unpack_lo<DT>(g) + B::template unpack_lo<DT>(r);
+    f32 hi = B::template unpack_hi<DT>(v) * B::template unpack_hi<DT>(g) + B::template unpack_hi<DT>(r);
+    return B::template pack<DT>(lo, hi);
+  }
+  static FFC_FN U4 fma4(const U4& v, const U4& g, const U4& r) {
+    U4 o; o.x = fma2(v.x, g.x, r.x); o.y = fma2(v.y, g.y, r.y); o.z = fma2(v.z, g.z, r.z); o.w = fma2(v.w, g.w, r.w);
+    return o;
+  }
+  static FFC_FN u32 sum2(u32 v, u32 r) {
+    f32 lo = B::template unpack_lo<DT>(v) + B::template unpack_lo<DT>(r);
+    f32 hi = B::template unpack_hi<DT>(v) + B::template unpack_hi<DT>(r);
+    return B::template pack<DT>(lo, hi);
+  }
+  static FFC_FN U4 sum4(const U4& v, const U4& r) {
+    U4 o; o.x = sum2(v.x, r.x); o.y = sum2(v.y, r.y); o.z = sum2(v.z, r.z); o.w = sum2(v.w, r.w);
     return o;
   }
   static FFC_FN U4 mask4(const U4& v, pred ok) {
@@ -993,15 +1037,16 @@ struct Body {
   }
   // rows_out of pass k0: y[n0 M + m] (+)= i^q y_k0[m], the last pass (* postgate), q = n0 k0 4/R: i^q (r + i s) = (r,s), (-s,r), (-r,-s),
   // (s,-r).  Passes k0 > 0 add to what the SAME wave stored in the earlier passes (its own column slice).
-  template <int NC>
+  // ADD: as rows_out -- the addend joins on the LAST pass only, after the gate multiplies the summed passes
+  template <int NC, bool ADD = B::HAS_ADD>
   static FFC_FN void rows_out_rp(const ConvArgs& a, int h, int pq, Unit un, Pass ps) {
-    if constexpr (B::FAST_ONLY) { rows_out_rp_t<NC, true>(a, h, pq, un, ps); return; }
+    if constexpr (B::FAST_ONLY) { rows_out_rp_t<NC, true, ADD>(a, h, pq, un, ps); return; }
     if constexpr (FFC_RP_HOIST != 0 && !B::LEAN_OUTER) {
-      if (a.fast) { rows_out_rp_t<NC, true>(a, h, pq, un, ps); return; }
+      if (a.fast) { rows_out_rp_t<NC, true, ADD>(a, h, pq, un, ps); return; }
     }
-    rows_out_rp_t<NC, false>(a, h, pq, un, ps);
+    rows_out_rp_t<NC, false, ADD>(a, h, pq, un, ps);
   }
-  template <int NC, bool FASTP>
+  template <int NC, bool FASTP, bool ADD = false>
   static FFC_FN void rows_out_rp_t(const ConvArgs& a, int h, int pq, Unit un, Pass ps) {
     // batches of chunks: the earlier passes' sums (passes k0 > 0) and, on the last pass, the output gate of a batch are requested
     // together ahead of the work on them (round 4; before: the sums up front in the forward kernels only, the gate chunk by chunk)
@@ -1012,19 +1057,21 @@ struct Body {
     const int fast = FASTP ? (a.stream ? 2 : 1) : (a.fast ? (a.stream ? 2 : 1) : 0);
     const int n0max = (a.L + GEO::N - 1) / GEO::N;
     const bool add_old = ps.k0 > 0, gate = a.postgate && ps.k0 == ps.R - 1;
-    int64_t ro[2], rg[2]; bool okb[2];
+    const bool addl = ADD && ps.k0 == ps.R - 1;
+    int64_t ro[2], rg[2], ra[2]; bool okb[2];
 #pragma unroll
     for (int pl = 0; pl < 2; pl++) {
       okb[pl] = (2 * pq + pl) < a.B;
       ro[pl] = row_off(2 * pq + pl, okb[pl], a.sby, h, a.L);
       rg[pl] = row_off(2 * pq + pl, okb[pl], a.sbp, h, a.L);
+      ra[pl] = ADD ? row_off(2 * pq + pl, okb[pl], a.sba, h, a.L) : 0;
     }
 #pragma unroll 1
     for (int n0 = 0; n0 < n0max; n0++) {
       const int q = (n0 * ps.k0 * (4 / ps.R)) & 3;
 #pragma unroll
       for (int ib = 0; ib < NC; ib += GB) {
-        U4 old[GB][2], G[GB][2];
+        U4 old[GB][2], G[GB][2], Rr[GB][2];
 #pragma unroll
         for (int jj = 0; jj < GB; jj++) {
           i32 idx = lane + (ib + jj) * 64;
@@ -1033,6 +1080,7 @@ struct Body {
           for (int pl = 0; pl < 2; pl++) {
             if (add_old) old[jj][pl] = gload8((const uint16_t*)a.y + ro[pl], n, a.L, fast, okb[pl]);
             if (gate) G[jj][pl] = gload8((const uint16_t*)a.postgate + rg[pl], n, a.L, fast, okb[pl]);
+            if constexpr (ADD) { if (addl) Rr[jj][pl] = gload8((const uint16_t*)a.addend + ra[pl], n, a.L, fast, okb[pl]); }
           }
         }
         B::sched_fence();
@@ -1058,7 +1106,12 @@ struct Body {
             // the passes' contributions are summed ungated; the output gate multiplies the sum, on the last pass only (the gate
             // load and its 28 VALU per 8 elements were 20 % of a pass's VALU count when every pass multiplied its own part)
             if (add_old) c = add4(old[jj][pl], c, sg);
-            if (gate) c = mul4(c, G[jj][pl]);
+            if constexpr (ADD) {
+              if (addl) c = gate ? fma4(c, G[jj][pl], Rr[jj][pl]) : sum4(c, Rr[jj][pl]);
+              else if (gate) c = mul4(c, G[jj][pl]);      // (never: gate implies the last pass)
+            } else {
+              if (gate) c = mul4(c, G[jj][pl]);
+            }
             gstore8((uint16_t*)a.y + ro[pl], n, a.L, fast, okb[pl], c);
           }
         }
@@ -2315,9 +2368,9 @@ struct Body {
         if constexpr (SZ) {
           if (a.yraw) {
             ConvArgs ar = a;
-            ar.y = a.yraw; ar.postgate = nullptr; ar.sby = (int64_t)a.H * a.L;
-            if constexpr (RP) rows_out_rp<NC>(ar, h, p, un, ps);
-            else rows_out<NC>(ar, h, p, un);
+            ar.y = a.yraw; ar.postgate = nullptr; ar.addend = nullptr; ar.sby = (int64_t)a.H * a.L;
+            if constexpr (RP) rows_out_rp<NC, false>(ar, h, p, un, ps);
+            else rows_out<NC, false>(ar, h, p, un);
           }
         }
         if constexpr (RP) rows_out_rp<NC>(a, h, p, un, ps);
@@ -2451,7 +2504,13 @@ struct Body {
                 if constexpr (SZ) {
                   if (a.yraw) gstore8_rows((uint16_t*)a.yraw, b, h, a, (int64_t)a.H * a.L, m, 1, b < a.B, v);      // output before the postgate
                 }
-                if (a.postgate) v = mul4(v, gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, 1, b < a.B));
+                if constexpr (B::HAS_ADD) {      // + addend, after Y is final and after the copy before the gate (ffc_conv_fwd_res)
+                  U4 r = gload8_rows((const uint16_t*)a.addend, b, h, a, a.sba, m, 1, b < a.B);
+                  if (a.postgate) v = fma4(v, gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, 1, b < a.B), r);
+                  else v = sum4(v, r);
+                } else {
+                  if (a.postgate) v = mul4(v, gload8_rows((const uint16_t*)a.postgate, b, h, a, a.sbp, m, 1, b < a.B));
+                }
                 gstore8_rows((uint16_t*)a.y, b, h, a, a.sby, m, 1, b < a.B, v);
               }
             }
@@ -2475,8 +2534,8 @@ struct Body {
             if constexpr (SZ) {
               if (a.yraw) {      // output before the postgate multiply (dpostgate = dout * this)
                 ConvArgs ar = a;
-                ar.y = a.yraw; ar.postgate = nullptr; ar.sby = (int64_t)a.H * a.L;
-                rows_out_rp<NCH>(ar, h, q, un, ps);
+                ar.y = a.yraw; ar.postgate = nullptr; ar.addend = nullptr; ar.sby = (int64_t)a.H * a.L;
+                rows_out_rp<NCH, false>(ar, h, q, un, ps);
               }
             }
             rows_out_rp<NCH>(a, h, q, un, ps);
@@ -2499,8 +2558,8 @@ struct Body {
           if constexpr (SZ) {
             if (a.yraw) {
               ConvArgs ar = a;
-              ar.y = a.yraw; ar.postgate = nullptr; ar.sby = (int64_t)a.H * a.L;
-              rows_out(ar, h, q, un);
+              ar.y = a.yraw; ar.postgate = nullptr; ar.addend = nullptr; ar.sby = (int64_t)a.H * a.L;
+              rows_out<NCH, false>(ar, h, q, un);
             }
           }
           rows_out(a, h, q, un);

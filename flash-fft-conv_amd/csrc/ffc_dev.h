@@ -37,6 +37,7 @@ struct DevB {
   struct U4 { u32 x, y, z, w; };
   static constexpr bool LEAN_OUTER = false;
   static constexpr bool FAST_ONLY = false;     // true: only the 16-byte arm of the row accesses is compiled (Body::gload8 / gstore8)
+  static constexpr bool HAS_ADD = false;       // true (DevBA): the forward's output epilogue adds ConvArgs::addend (ffc_conv_fwd_res)
   using A16 = f32x16;   // 16 consecutive VGPRs/AGPRs: the MFMA accumulator tuple
   using W4 = u32x4v;    // 4 consecutive VGPRs: one MFMA A/B operand
   static constexpr bool HAS_TR = true;
@@ -264,6 +265,12 @@ __device__ __forceinline__ bool map_block(int H, int nchunk, int* h, int* chunk)
   return *h < H;
 }
 
+// DevB for the forward kernels with an addend in the output epilogue (y = postgate * conv + addend, ffc_conv_fwd_res): kernel
+// instantiations of their own, so that the kernels without an addend keep their code and registers
+struct DevBA : DevB {
+  static constexpr bool HAS_ADD = true;
+};
+
 // DevB with an opaque lane id: every use site re-derives its lane-dependent values, nothing lane-derived is
 // hoisted out of the per-pair loop.  The backward kernels run on a 128-VGPR budget (see Modes::WAcc); hoisted
 // invariants there would overflow into the accumulation registers that hold the dk_f partial sums.
@@ -318,6 +325,7 @@ static inline int ffc_fail(const std::string& m) { ffc_set_error_(m.c_str()); re
 // device with the first device's setting only.
 int ffc_set_lds_once(const void* kernel, int bytes);      // ffc_hip.hip
 namespace ffc { struct DkfArgs; }
+int ffc_conv_res_launch(int N, int dtype, const ffc::ConvArgs& a, hipStream_t st);      // ffc_k_conv_res.hip: forward with an addend in the output epilogue
 int ffc_bwdz_launch(int N, int dtype, const ffc::DkfArgs& d, hipStream_t st);      // ffc_k_bwdz.hip: fused backward on saved spectra
 template <class K>
 static int ffc_set_lds(K kernel, int bytes) { return ffc_set_lds_once((const void*)kernel, bytes); }

@@ -187,19 +187,21 @@ extern "C" int64_t ffc_spectrum_bytes(const ffc_plan* p, int64_t B, int64_t H) {
 static int conv_fwd_impl(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate,
                          void* y, void* zsave, void* yraw, int sparse, int64_t B, int64_t H, int64_t L, int conj_kf, int64_t sb_u, int64_t sb_pre,
                          int64_t sb_post, int64_t sb_y, void* stream, const float* kfuse_k = nullptr, int64_t kfuse_Lk = 0,
-                         bool* kfuse_done = nullptr, const void* kfuse_x = nullptr, float kfuse_xscale = 1.0f) {
+                         bool* kfuse_done = nullptr, const void* kfuse_x = nullptr, float kfuse_xscale = 1.0f, const void* addend = nullptr,
+                         int64_t sb_add = 0) {
   if (!p || !u || !kf || !y) return ffc_fail("null arg");
   if (B <= 0 || H <= 0) return ffc_fail("empty batch/heads");
   if (L <= 0 || L > p->hp.N) return ffc_fail("L must be in (0, fft_size]");
   if ((uintptr_t)kf & 15) return ffc_fail("k_f must be 16-byte aligned");
   if (!ffc_stride_ok(&sb_u, B, H, L) || !ffc_stride_ok(&sb_pre, B, H, L) || !ffc_stride_ok(&sb_post, B, H, L) ||
-      !ffc_stride_ok(&sb_y, B, H, L))
+      !ffc_stride_ok(&sb_y, B, H, L) || !ffc_stride_ok(&sb_add, B, H, L))
     return ffc_fail("tensor too large (>= 2^31 elements) or batch stride smaller than H*L");
   ConvArgs a{};
   a.u = u; a.pregate = pregate; a.postgate = postgate; a.y = y; a.kf = kf;
   a.tab = p->d_blob; a.t = p->hp.tabs;
   a.B = (int)B; a.H = (int)H; a.L = (int)L; a.npair = (int)((B + 1) / 2);
   a.sbu = sb_u; a.sbg = sb_pre; a.sbp = sb_post; a.sby = sb_y;
+  a.addend = addend; a.sba = sb_add;
   a.conj_kf = conj_kf;
   // y_raw without the spectra: the single-tile sizes (fft <= 2048) only -- their backward transforms u * pregate again from rows it
   // loads anyway (dpregate, du) and takes dpostgate = dout * y_raw from its dout row load (round 6)
@@ -210,8 +212,8 @@ static int conv_fwd_impl(const ffc_plan* p, const void* u, const void* kf, const
   if (zsave && (ffc_spectrum_bytes(p, B, H) == 0 || ((uintptr_t)zsave & 15))) return ffc_fail("spectrum buffer: unsupported plan or misaligned");
   a.s_inv = (float)p->hp.s_inv; a.s_fwd = (float)p->hp.s_fwd;
   a.flags = p->env_flags;
-  a.fast = (L % 8 == 0) && !(((uintptr_t)u | (uintptr_t)y | (uintptr_t)pregate | (uintptr_t)postgate) & 15) &&
-           !((sb_u | sb_pre | sb_post | sb_y) & 7);
+  a.fast = (L % 8 == 0) && !(((uintptr_t)u | (uintptr_t)y | (uintptr_t)pregate | (uintptr_t)postgate | (uintptr_t)addend) & 15) &&
+           !((sb_u | sb_pre | sb_post | sb_y | sb_add) & 7);
   ffc_choose_chunks(p, a.H, a.npair, &a.nchunk, &a.ppc, true);
   a.persist = ffc_persist(p);
   a.R = p->hp.R;
@@ -232,6 +234,7 @@ static int conv_fwd_impl(const ffc_plan* p, const void* u, const void* kf, const
   }
   // every row is read / written exactly once per launch (multi-pass sizes re-read the rows in every pass: plain accesses)
   a.stream = p->env_stream >= 0 ? p->env_stream : (p->hp.R > 1 ? 0 : 1);
+  if (addend) return ffc_conv_res_launch(p->hp.N, p->hp.dtype, a, (hipStream_t)stream);      // kernels of their own (ffc_k_conv_res.hip)
   return ffc_dispatch<ConvLaunch>(p->hp.N, p->hp.dtype, a, (hipStream_t)stream);
 }
 
@@ -248,6 +251,26 @@ extern "C" int ffc_conv_fwd_z(const ffc_plan* p, const void* u, const void* kf, 
   if (!zsave && !(y_raw && p && p->hp.N1 <= 1)) return ffc_fail("null spectrum buffer (y_raw alone: single-tile sizes, fft <= 2048)");
   if (y_raw && ((uintptr_t)y_raw & 15)) return ffc_fail("y_raw must be 16-byte aligned");
   return conv_fwd_impl(p, u, kf, pregate, postgate, y, zsave, y_raw, 0, B, H, L, 0, sb_u, sb_pre, sb_post, sb_y, stream);
+}
+
+// y = postgate * conv(u * pregate, k) + addend: the superset of ffc_conv_fwd_strided and ffc_conv_fwd_z (zsave / y_raw nullable, y_raw
+// stays the output before gate and addend).  The multi-pass sizes read-modify-write y between their passes, so an addend that overlaps y
+// is refused at every size.
+extern "C" int ffc_conv_fwd_res(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate,
+                                const void* addend, void* y, void* zsave, void* y_raw, int64_t B, int64_t H, int64_t L, int conj_kf,
+                                int64_t sb_u, int64_t sb_pre, int64_t sb_post, int64_t sb_add, int64_t sb_y, void* stream) {
+  if (!p) return ffc_fail("null arg");
+  if (y_raw && !zsave && p->hp.N1 > 1) return ffc_fail("y_raw without a spectrum buffer: single-tile sizes only (fft <= 2048)");
+  if (y_raw && ((uintptr_t)y_raw & 15)) return ffc_fail("y_raw must be 16-byte aligned");
+  if ((zsave || y_raw) && conj_kf) return ffc_fail("spectrum buffer / y_raw: forward pass only (conj_kf = 0)");
+  if (addend && y && B > 0 && H > 0 && L > 0) {
+    const int64_t sa = sb_add ? sb_add : H * L, sy = sb_y ? sb_y : H * L;
+    const uintptr_t a0 = (uintptr_t)addend, a1 = a0 + (uintptr_t)(((B - 1) * sa + H * L) * 2);
+    const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)(((B - 1) * sy + H * L) * 2);
+    if (a0 < y1 && y0 < a1) return ffc_fail("addend overlaps y");
+  }
+  return conv_fwd_impl(p, u, kf, pregate, postgate, y, zsave, y_raw, 0, B, H, L, conj_kf, sb_u, sb_pre, sb_post, sb_y, stream,
+                       nullptr, 0, nullptr, nullptr, 1.0f, addend, sb_add);
 }
 
 // Forward / input-gradient pass with a LOW-PASS k_f: every non-zero bin f has k3 = f / (N1 N2) < rows or >= 32 - rows

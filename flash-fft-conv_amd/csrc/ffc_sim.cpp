@@ -63,6 +63,7 @@ static inline uint16_t f32_to_dt(int DT, float f) { return DT == DT_BF16 ? f32_t
 struct SimB {
   static constexpr bool LEAN_OUTER = false;
   static constexpr bool FAST_ONLY = false;
+  static constexpr bool HAS_ADD = false;
   using f32 = Vec<float>;
   using i32 = Vec<int>;
   using u32 = Vec<uint32_t>;
@@ -312,6 +313,7 @@ struct SimB {
 bool SimB::HAS_TR = true;
 // mirrors DevBO: the backward kernels use the per-tile outer stages
 struct SimBO : SimB { static constexpr bool LEAN_OUTER = true; };
+struct SimBA : SimB { static constexpr bool HAS_ADD = true; };           // forward kernels with an addend in the output epilogue (DevBA)
 struct SimBOF : SimBO { static constexpr bool FAST_ONLY = true; };      // the fast-only instantiation of the multi-pass backward (DevBOF)
 static bool g_force_slow = false;
 
@@ -329,61 +331,67 @@ static void run_wg(int nwaves, int lds_bytes, F fn) {
   pthread_barrier_destroy(&ctx.bar);
 }
 
-template <class GEO, int DT>
+// SB: SimB, or SimBA for the forward with an addend (ffcsim_conv_fwd_res; no k -> k_f step and no frequency-sparse form there)
+template <class GEO, int DT, class SB = SimB>
 static void sim_conv_t(const ConvArgs& a) {
   for (int h = 0; h < a.H; h++)
     for (int c = 0; c < a.nchunk; c++) {
       if constexpr (GEO::N == 32768) {
         if (a.R > 1) {       // mirrors conv_kernel<..., RP = true>: the passes run one after the other in the same workgroup
           run_wg(GEO::WGW, GEO::LDS_BYTES, [&]() {
-            Body<SimB, GEO, DT>::setup_tables(a.tab, a.t);
-            if (16 * GEO::Mi >= a.L) Body<SimB, GEO, DT>::template conv_job<true, true>(a, h, c);
-            else Body<SimB, GEO, DT>::template conv_job<false, true>(a, h, c);
+            Body<SB, GEO, DT>::setup_tables(a.tab, a.t);
+            if (a.zsave) {      // conv_rp_kernel<.., SZ> (ffcsim_conv_fwd_res only: ffcsim_conv_fwd passes no spectrum buffer here)
+              if (16 * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv_job<true, true, true>(a, h, c);
+              else Body<SB, GEO, DT>::template conv_job<false, true, true>(a, h, c);
+              return;
+            }
+            if (16 * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv_job<true, true>(a, h, c);
+            else Body<SB, GEO, DT>::template conv_job<false, true>(a, h, c);
           });
           continue;
         }
       }
       if constexpr (GEO::N == 1024) {
         if (a.R > 1) {       // inner-only multi-pass form (fft 2048)
-          run_wg(GEO::WGW, GEO::LDS_BYTES + a.R * Body<SimB, GEO, DT>::IPASS_BYTES, [&]() {
-            Body<SimB, GEO, DT>::setup_tables(a.tab, a.t);
-            Body<SimB, GEO, DT>::setup_tables_ipass(a.tab, a.t, a.R);
-            if (a.zsave || a.yraw) Body<SimB, GEO, DT>::template conv_job<false, true, true>(a, h, c);      // conv_rp_kernel<.., SZ>
-            else Body<SimB, GEO, DT>::template conv_job<false, true>(a, h, c);
+          run_wg(GEO::WGW, GEO::LDS_BYTES + a.R * Body<SB, GEO, DT>::IPASS_BYTES, [&]() {
+            Body<SB, GEO, DT>::setup_tables(a.tab, a.t);
+            Body<SB, GEO, DT>::setup_tables_ipass(a.tab, a.t, a.R);
+            if (a.zsave || a.yraw) Body<SB, GEO, DT>::template conv_job<false, true, true>(a, h, c);      // conv_rp_kernel<.., SZ>
+            else Body<SB, GEO, DT>::template conv_job<false, true>(a, h, c);
           });
           continue;
         }
       }
       run_wg(GEO::WGW, GEO::LDS_BYTES, [&]() {
-        if constexpr (GEO::HAS_SP) {      // frequency-sparse variant (ffc_conv_fwd_sparse)
+        if constexpr (GEO::HAS_SP && !SB::HAS_ADD) {      // frequency-sparse variant (ffc_conv_fwd_sparse)
           if (a.sparse) {
-            if ((GEO::N1 / 2) * GEO::Mi >= a.L) Body<SimB, GEO, DT>::template conv<true, false, true>(a, h, c);
-            else Body<SimB, GEO, DT>::template conv<false, false, true>(a, h, c);
+            if ((GEO::N1 / 2) * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv<true, false, true>(a, h, c);
+            else Body<SB, GEO, DT>::template conv<false, false, true>(a, h, c);
             return;
           }
         }
-        if constexpr (GEO::OUTER && GEO::NW > 1) {
+        if constexpr (GEO::OUTER && GEO::NW > 1 && !SB::HAS_ADD) {
           if (a.kfuse_k || a.kfuse_x) {   // k -> k_f of this head inside the same workgroup (conv_kernel, ConvArgs::kfuse_k / kfuse_x)
-            Body<SimB, GEO, DT>::setup_tables(a.tab, a.t);
-            Modes<SimB, GEO, DT>::kfft_head(a, h);
+            Body<SB, GEO, DT>::setup_tables(a.tab, a.t);
+            Modes<SB, GEO, DT>::kfft_head(a, h);
             const bool half = (GEO::N1 / 2) * GEO::Mi >= a.L;
-            if (a.zsave) { if (half) Body<SimB, GEO, DT>::template conv_job<true, false, true>(a, h, c); else Body<SimB, GEO, DT>::template conv_job<false, false, true>(a, h, c); }
-            else { if (half) Body<SimB, GEO, DT>::template conv_job<true>(a, h, c); else Body<SimB, GEO, DT>::template conv_job<false>(a, h, c); }
+            if (a.zsave) { if (half) Body<SB, GEO, DT>::template conv_job<true, false, true>(a, h, c); else Body<SB, GEO, DT>::template conv_job<false, false, true>(a, h, c); }
+            else { if (half) Body<SB, GEO, DT>::template conv_job<true>(a, h, c); else Body<SB, GEO, DT>::template conv_job<false>(a, h, c); }
             return;
           }
         }
         if constexpr (GEO::OUTER) {       // the launcher's HALF variant
           if (a.zsave) {                  // spectrum-saving training forward (ffc_conv_fwd_z)
-            if ((GEO::N1 / 2) * GEO::Mi >= a.L) Body<SimB, GEO, DT>::template conv<true, true>(a, h, c);
-            else Body<SimB, GEO, DT>::template conv<false, true>(a, h, c);
+            if ((GEO::N1 / 2) * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv<true, true>(a, h, c);
+            else Body<SB, GEO, DT>::template conv<false, true>(a, h, c);
             return;
           }
-          if ((GEO::N1 / 2) * GEO::Mi >= a.L) { Body<SimB, GEO, DT>::template conv<true>(a, h, c); return; }
+          if ((GEO::N1 / 2) * GEO::Mi >= a.L) { Body<SB, GEO, DT>::template conv<true>(a, h, c); return; }
         } else {
           // single-tile sizes: the training forward that keeps the spectra and / or the output before the postgate (conv_kernel<.., SZ>)
-          if (a.zsave || a.yraw) { Body<SimB, GEO, DT>::template conv<false, true>(a, h, c); return; }
+          if (a.zsave || a.yraw) { Body<SB, GEO, DT>::template conv<false, true>(a, h, c); return; }
         }
-        Body<SimB, GEO, DT>::conv(a, h, c);
+        Body<SB, GEO, DT>::conv(a, h, c);
       });
     }
 }
@@ -411,6 +419,7 @@ static int dispatch(int N, int dtype, A&&... args) {
   return -1;
 }
 template <class GEO, int DT> struct ConvRun { static void run(const ConvArgs& a) { sim_conv_t<GEO, DT>(a); } };
+template <class GEO, int DT> struct ConvResRun { static void run(const ConvArgs& a) { sim_conv_t<GEO, DT, SimBA>(a); } };
 template <class GEO, int DT> struct KfRun {
   static void run(const KfArgs& a) {
     const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
@@ -571,6 +580,37 @@ int ffcsim_conv_fwd(int N, int dtype, const void* u, const void* kf, const void*
     a.kfuse_k = g_kfuse_k; a.kfuse_Lk = g_kfuse_lk; a.kfuse_scale = (float)(p.s_k / p.s_fwd) / (dtype == DT_F16 ? 256.f : 1.f); a.kfuse_fast = (g_kfuse_lk % 4 == 0) && !g_force_slow;
   }
   return dispatch<ConvRun>(N, dtype, a);
+}
+
+// Same contract as ffc_conv_fwd_res (include/flashfftconv_hip.h) on host memory: the forward with an addend in the output epilogue, batch
+// strides in elements (0 = contiguous), optional spectrum buffer / output before gate and addend.  -3: y_raw without a spectrum buffer
+// at a size with an outer digit, -4: the addend overlaps y.
+int ffcsim_conv_fwd_res(int N, int dtype, const void* u, const void* kf, const void* pregate, const void* postgate, const void* addend,
+                        void* y, void* zsave, void* y_raw, int B, int H, int L, int conj_kf, int64_t sb_u, int64_t sb_pre, int64_t sb_post,
+                        int64_t sb_add, int64_t sb_y) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (L > N || L <= 0 || B <= 0 || H <= 0) return -2;
+  if (y_raw && !zsave && p.N1 > 1) return -3;
+  const int64_t hl = (int64_t)H * L;
+  if (!sb_u) sb_u = hl; if (!sb_pre) sb_pre = hl; if (!sb_post) sb_post = hl; if (!sb_add) sb_add = hl; if (!sb_y) sb_y = hl;
+  if (sb_u < hl || sb_pre < hl || sb_post < hl || sb_add < hl || sb_y < hl) return -2;
+  if (addend) {
+    const uintptr_t a0 = (uintptr_t)addend, a1 = a0 + (uintptr_t)(((B - 1) * sb_add + hl) * 2);
+    const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)(((B - 1) * sb_y + hl) * 2);
+    if (a0 < y1 && y0 < a1) return -4;
+  }
+  ConvArgs a{};
+  a.u = u; a.pregate = pregate; a.postgate = postgate; a.y = y; a.kf = kf; a.addend = addend;
+  a.tab = p.blob.data(); a.t = p.tabs;
+  a.B = B; a.H = H; a.L = L; a.npair = (B + 1) / 2;
+  a.sbu = sb_u; a.sbg = sb_pre; a.sbp = sb_post; a.sby = sb_y; a.sba = sb_add;
+  a.nchunk = 1; a.ppc = a.npair; a.conj_kf = conj_kf; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !((sb_u | sb_pre | sb_post | sb_y | sb_add) & 7) && !g_force_slow;
+  a.R = p.R;
+  a.zsave = zsave; a.yraw = y_raw;
+  if (!addend) return dispatch<ConvRun>(N, dtype, a);
+  return dispatch<ConvResRun>(N, dtype, a);
 }
 
 

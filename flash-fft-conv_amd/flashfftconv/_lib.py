@@ -34,6 +34,7 @@ def lib():
         L.ffc_conv_bwd_gated_strided.argtypes = [c_vp] * 10 + [c_i64] * 10 + [c_vp]
         L.ffc_spectrum_bytes.argtypes = [c_vp, c_i64, c_i64]; L.ffc_spectrum_bytes.restype = c_i64
         L.ffc_conv_fwd_z.argtypes = [c_vp] * 8 + [c_i64] * 7 + [c_vp]
+        L.ffc_conv_fwd_res.argtypes = [c_vp] * 9 + [c_i64] * 3 + [c_int] + [c_i64] * 5 + [c_vp]
         L.ffc_conv_bwd_z.argtypes = [c_vp] * 11 + [c_i64] * 10 + [c_vp]
         L.ffc_conv_bwd_zy.argtypes = [c_vp] * 12 + [c_i64] * 10 + [c_vp]
         L.ffc_conv_fwd_k.argtypes = [c_vp, c_vp, c_i64] + [c_vp] * 7 + [c_i64] * 3 + [c_vp]

@@ -156,6 +156,13 @@ def _sparse_rows(mod, plan):
     return rows if 1 <= rows <= 4 else 0
 
 
+class _SeqlenOnly:
+    """stand-in for a plan where only its fft size is read (_sparse_rows ahead of any device work)"""
+
+    def __init__(self, seqlen):
+        self.seqlen = seqlen
+
+
 def _conv_sparse(plan, u, kf, pregate, postgate, conj, rows):
     B, H, L = u.shape
     y = torch.empty_like(u)
@@ -243,6 +250,17 @@ def _conv_save(plan, u, kf, pregate, postgate, z, yraw=None):
     y = torch.empty_like(u)
     _lib.check(_lib.lib().ffc_conv_fwd_z(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(y),
                                          _lib.ptr(z), _lib.ptr(yraw), B, H, L, 0, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_z")
+    return y
+
+
+def _conv_res(plan, u, kf, pregate, postgate, residual, z=None, yraw=None):
+    """y = postgate * conv(u * pregate, k) + residual, the residual added in the kernel's output epilogue (ffc_conv_fwd_res);
+    z / yraw as _conv_save (yraw: the output before gate and residual)"""
+    B, H, L = u.shape
+    y = torch.empty_like(u)
+    _lib.check(_lib.lib().ffc_conv_fwd_res(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(residual),
+                                           _lib.ptr(y), _lib.ptr(z), _lib.ptr(yraw), B, H, L, 0, 0, 0, 0, 0, 0, _lib.stream_ptr()),
+               "ffc_conv_fwd_res")
     return y
 
 
@@ -579,17 +597,30 @@ def _check_inputs(mod, u, k, gates):
             raise RuntimeError("FlashFFTConv: gates must match u in shape and dtype")
 
 
+def _check_residual(u, residual):
+    if not torch.is_tensor(residual):
+        raise RuntimeError("FlashFFTConv: residual must be a tensor")
+    if residual.device != u.device:
+        raise RuntimeError(f"FlashFFTConv: residual is on {residual.device}, u on {u.device}")
+    if residual.shape != u.shape or residual.dtype != u.dtype:
+        raise RuntimeError("FlashFFTConv: residual must match u in shape and dtype")
+
+
 class _FlashFFTConvFn(torch.autograd.Function):
     # reference: FlashFFTConvFunc (conv.py:563) and GatedFlashFFTConvFunc (conv.py:3236)
 
     @staticmethod
-    def forward(ctx, u, k, mod, pregate, postgate):
+    def forward(ctx, u, k, mod, pregate, postgate, residual=None):
         _check_inputs(mod, u, k, (pregate, postgate))
+        if residual is not None:
+            _check_residual(u, residual)
         with _dev_ctx(u.device):      # launches go to u's device and its current stream
-            return _FlashFFTConvFn._forward(ctx, u, k, mod, pregate, postgate)
+            return _FlashFFTConvFn._forward(ctx, u, k, mod, pregate, postgate, residual)
 
     @staticmethod
-    def _forward(ctx, u, k, mod, pregate, postgate):
+    def _forward(ctx, u, k, mod, pregate, postgate, residual=None):
+        # residual: added in the convolution kernel's output epilogue (fused routes only: FlashFFTConv.forward composes the others)
+        residual = None if residual is None else residual.contiguous()
         u = u.contiguous()
         pregate = None if pregate is None else pregate.contiguous()
         postgate = None if postgate is None else postgate.contiguous()
@@ -616,7 +647,8 @@ class _FlashFFTConvFn(torch.autograd.Function):
             plan = mod._get_plan(u.device, mod._plan_seqlen)
             kf = mod._cached_kf(k) if mod.cache_kf and not k.requires_grad else None
             # one C-ABI call for k -> k_f + the convolution (ffc_conv_fwd_k) unless something sits between the two
-            one_call = kf is None and not mod._folded and mod._kf_keep is None
+            # (a residual takes k -> k_f + ffc_conv_fwd_res: the one-call entry point has no addend)
+            one_call = kf is None and not mod._folded and mod._kf_keep is None and residual is None
             if kf is None and not one_call:
                 kf = _kernel_fft(plan, _periodise_k(k, mod.seqlen) if mod._folded else k)
                 if mod._kf_keep is not None:       # frequency-sparse k_f (flashfftconv/sparse_conv.py)
@@ -654,6 +686,10 @@ class _FlashFFTConvFn(torch.autograd.Function):
                                                      _lib.stream_ptr()), "ffc_conv_fwd_k")
                 if mod.cache_kf and not k.requires_grad:
                     mod._kf_cache = (_kf_key(k), kf)
+            elif residual is not None:
+                if rows:
+                    raise RuntimeError("FlashFFTConv: internal: residual on the compute-skipping frequency-sparse kernel")
+                out = _conv_res(plan, u, kf, pregate, postgate, residual, z, yraw)
             elif not rows:
                 out = (_conv(plan, u, kf, pregate, postgate, False) if z is None and yraw is None
                        else _conv_save(plan, u, kf, pregate, postgate, z, yraw))
@@ -673,7 +709,9 @@ class _FlashFFTConvFn(torch.autograd.Function):
         if not ctx.saved_tensors:
             raise RuntimeError("FlashFFTConv: backward needs module.training=True at forward time")
         with _dev_ctx(ctx.saved_tensors[0].device):
-            return _FlashFFTConvFn._backward(ctx, dout)
+            grads = _FlashFFTConvFn._backward(ctx, dout)
+        # y = (...) + residual: the residual's gradient is dout itself; the other gradients never see it
+        return grads + (dout if ctx.needs_input_grad[5] else None,)      # (every caller passes the residual slot, None included)
 
     @staticmethod
     def _backward(ctx, dout):
@@ -821,6 +859,7 @@ class FlashFFTConv(torch.nn.Module):
             for c in fitted.values():
                 if c is not m:
                     c._kf_cache = None
+                    c.__dict__.pop("_kf_cache_res", None)      # (the fused operator's second slot, flashfftconv/hyena.py)
         return m
 
     def graphed_step(self, u, k, dout, pregate=None, postgate=None, warmup=3):
@@ -866,11 +905,29 @@ class FlashFFTConv(torch.nn.Module):
             del state_dict[key]
         super()._load_from_state_dict(state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs)
 
-    def forward(self, u, k, pregate=None, postgate=None):
+    def _residual_composes(self, Lmax):
+        """routes without a fused epilogue for the residual: the HBM-level sizes and the compute-skipping frequency-sparse kernel"""
+        if self._big or self._route_big(Lmax):
+            return True
+        return _sparse_rows(self, _SeqlenOnly(self._plan_seqlen)) > 0
+
+    def forward(self, u, k, pregate=None, postgate=None, residual=None):
+        """y = postgate * conv(u * pregate, k) + residual (gates: both or none; residual optional).
+
+        residual (u's shape, dtype and device; a skip connection or a second branch) is added in the convolution kernel's output
+        epilogue -- fp32 product and sum, one rounding -- on every fused route (fft <= 131072), with no elementwise kernel behind the
+        convolution; its gradient is the incoming gradient, all other gradients are those of the call without it.  Two routes have no
+        fused epilogue: the HBM-level sizes (fft >= 262144, and fft 131072 with rows longer than half of it) and the compute-skipping
+        frequency-sparse kernel; there the module returns conv(u, k, pregate, postgate) + residual by composition (two roundings)."""
         if pregate is not None or postgate is not None:
             assert pregate is not None and postgate is not None
         if self.seqlen > 32768 and torch.is_tensor(u) and torch.is_tensor(k) and u.dim() == 3 and k.dim() == 2:
             n = self._fit_seqlen(u.shape[-1], k.shape[-1])
             if n != self.seqlen:
-                return self._fitted_module(n)(u, k, pregate, postgate)
-        return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate)
+                return self._fitted_module(n)(u, k, pregate, postgate, residual)
+        if residual is not None:
+            _check_inputs(self, u, k, (pregate, postgate))
+            _check_residual(u, residual)
+            if self._residual_composes(max(u.shape[-1], k.shape[-1])):
+                return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, None) + residual
+        return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, residual)

@@ -8,11 +8,16 @@ The reference's callers build the gated long convolution out of separate kernels
     x1v = (x1 * v).contiguous()                    # elementwise kernel + copy
     y = flashfftconv(x1v, k)                       # FFT convolution
     y = y * x2                                     # elementwise kernel
+    y = y + flashfftconv(v.contiguous(), k2)       # M2-BERT with residual_long_conv=True: copy, second convolution, add kernel
 
 Here the three slices are handed to the gated FFT-conv kernel IN PLACE (batch-strided rows, ffc_conv_fwd_strided): v is the
 input, x1 the pregate, x2 the postgate, so the multiply kernels, the copy and their HBM round trips disappear, in the forward
 and in the backward (du / dpregate / dpostgate are written straight into the slices of d(uc), one launch; then the short
-convolution's own backward).  y = x2 * conv(x1 * v, k): the same function as the reference composition."""
+convolution's own backward).  y = x2 * conv(x1 * v, k): the same function as the reference composition.
+
+With k_res (the M2 residual long convolution, monarch_mixer_sequence_mixer_flashfftconv.py:151-175) y = x2 * conv(x1 * v, k) +
+conv(v, k_res) in two launches: conv(v, k_res) reading the v slice in place, then the gated kernel with that result as the addend of its
+output epilogue (ffc_conv_fwd_res) -- no copy of v and no add kernel."""
 import torch
 
 from . import _lib
@@ -25,10 +30,11 @@ def _slice_ptr(t, j, D, L):
 
 
 class _GatedSlicesFn(torch.autograd.Function):
-    """y = uc[:, 1] * conv(uc[:, 0] * uc[:, 2], k) for uc viewed as (B, 3, D, L): x1 = slice 0, x2 = slice 1, v = slice 2."""
+    """y = uc[:, 1] * conv(uc[:, 0] * uc[:, 2], k) [+ conv(uc[:, 2], k_res)] for uc viewed as (B, 3, D, L): x1 = slice 0, x2 = slice 1,
+    v = slice 2."""
 
     @staticmethod
-    def forward(ctx, uc, k, mod):
+    def forward(ctx, uc, k, mod, k_res=None):
         B, D3, L = uc.shape
         D = D3 // 3
         plan = mod._get_plan(uc.device, mod._plan_seqlen)
@@ -40,6 +46,19 @@ class _GatedSlicesFn(torch.autograd.Function):
                     mod._kf_cache = (_kf_key(k), kf)
             y = torch.empty(B, D, L, dtype=uc.dtype, device=uc.device)
             sb = D3 * L
+            kf_res = yu = None
+            if k_res is not None:
+                # launch 1: yu = conv(v, k_res), v read in place; its k_f has a cache slot of its own (k and k_res would evict each other)
+                cache_res = mod.cache_kf and not k_res.requires_grad
+                c = getattr(mod, "_kf_cache_res", None) if cache_res else None
+                kf_res = c[1] if c is not None and c[0] == _kf_key(k_res) else None
+                if kf_res is None:
+                    kf_res = _kernel_fft(plan, _periodise_k(k_res, mod.seqlen) if mod._folded else k_res)
+                    if cache_res:
+                        mod._kf_cache_res = (_kf_key(k_res), kf_res)
+                yu = torch.empty_like(y)
+                _lib.check(_lib.lib().ffc_conv_fwd_strided(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf_res), None, None, _lib.ptr(yu),
+                                                           B, D, L, 0, sb, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_strided")
             # training: keep the spectra FFT(x1 * v) and the output before the x2 multiply (FlashFFTConv.save_spectrum)
             z = yraw = None
             if mod.training and mod.save_spectrum and _recording() and any(ctx.needs_input_grad[:2]):
@@ -49,7 +68,12 @@ class _GatedSlicesFn(torch.autograd.Function):
                         yraw = torch.empty_like(y)
                     except torch.cuda.OutOfMemoryError:
                         z = None
-            if z is None:
+            if yu is not None:
+                # launch 2: the gated kernel with yu as the addend of its output epilogue (z / yraw nullable: the output before x2 and yu)
+                _lib.check(_lib.lib().ffc_conv_fwd_res(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf), _slice_ptr(uc, 0, D, L),
+                                                       _slice_ptr(uc, 1, D, L), _lib.ptr(yu), _lib.ptr(y), _lib.ptr(z), _lib.ptr(yraw), B, D, L,
+                                                       0, sb, sb, sb, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_res")
+            elif z is None:
                 _lib.check(_lib.lib().ffc_conv_fwd_strided(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf), _slice_ptr(uc, 0, D, L),
                                                            _slice_ptr(uc, 1, D, L), _lib.ptr(y), B, D, L, 0, sb, sb, sb, 0,
                                                            _lib.stream_ptr()), "ffc_conv_fwd_strided")
@@ -58,8 +82,9 @@ class _GatedSlicesFn(torch.autograd.Function):
                                                      _slice_ptr(uc, 1, D, L), _lib.ptr(y), _lib.ptr(z), _lib.ptr(yraw), B, D, L,
                                                      sb, sb, sb, 0, _lib.stream_ptr()), "ffc_conv_fwd_z")
         ctx.mod, ctx.k_len, ctx.k_dtype = mod, k.shape[-1], k.dtype
+        ctx.res = None if k_res is None else (k_res.shape[-1], k_res.dtype)
         if mod.training:
-            ctx.save_for_backward(*((uc, kf) + (() if z is None else (z, yraw))))
+            ctx.save_for_backward(*((uc, kf) + (() if z is None else (z, yraw)) + (() if kf_res is None else (kf_res,))))
         return y
 
     @staticmethod
@@ -67,7 +92,11 @@ class _GatedSlicesFn(torch.autograd.Function):
         if not ctx.saved_tensors:
             raise RuntimeError("FlashHyenaOp: backward needs module.training=True at forward time")
         uc, kf = ctx.saved_tensors[:2]
-        z, yraw = ctx.saved_tensors[2:4] if len(ctx.saved_tensors) > 2 else (None, None)
+        rest = ctx.saved_tensors[2:]
+        kf_res = None
+        if ctx.res is not None:
+            rest, kf_res = rest[:-1], rest[-1]
+        z, yraw = rest[:2] if len(rest) >= 2 else (None, None)
         mod = ctx.mod
         B, D3, L = uc.shape
         D = D3 // 3
@@ -97,34 +126,58 @@ class _GatedSlicesFn(torch.autograd.Function):
             if mod._folded:
                 n = mod.seqlen
                 dk = (dk[:, :n] + dk[:, n:])[:, :ctx.k_len]
-        return duc, dk.to(ctx.k_dtype), None
+            dk_res = None
+            if kf_res is not None:
+                # the residual branch yu = conv(v, k_res): the ungated fused backward on (dy, v in place, kf_res) -> dk_res and a (B, D, L)
+                # input gradient, added into v's slice of duc (the workspace is free again: stream order)
+                dv = torch.empty_like(dy)
+                _lib.check(lib.ffc_conv_bwd_gated_strided(plan.handle, _lib.ptr(dy), _slice_ptr(uc, 2, D, L), _lib.ptr(kf_res), None, None,
+                                                          _lib.ptr(dv), None, None, _lib.ptr(ws), B, D, L, 0, sb, 0, 0, 0, 0, 0,
+                                                          _lib.stream_ptr()), "ffc_conv_bwd_gated_strided")
+                kr_len = plan.seqlen if mod._folded else ctx.res[0]
+                dk_res = torch.empty(D, kr_len, dtype=torch.float32, device=uc.device)
+                _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, kr_len, _lib.ptr(dk_res), _lib.stream_ptr()),
+                           "ffc_kernel_ifft_grad")
+                if mod._folded:
+                    n = mod.seqlen
+                    dk_res = (dk_res[:, :n] + dk_res[:, n:])[:, :ctx.res[0]]
+                dk_res = dk_res.to(ctx.res[1])
+                duc[:, 2 * D:].add_(dv)
+        return duc, dk.to(ctx.k_dtype), None, dk_res
 
 
-def gated_conv_from_slices(conv, uc, k):
-    """y = x2 * conv(x1 * v, k) with (x1, x2, v) = uc.split(D, dim=1), uc (B, 3D, L) contiguous, through `conv`
+def gated_conv_from_slices(conv, uc, k, k_res=None):
+    """y = x2 * conv(x1 * v, k) [+ conv(v, k_res)] with (x1, x2, v) = uc.split(D, dim=1), uc (B, 3D, L) contiguous, through `conv`
     (a FlashFFTConv).  Sizes served by the fused kernels (fft <= 131072) read the slices in place; larger ones fall back to
-    the module's gated call on contiguous copies (same result)."""
+    the module's gated call on contiguous copies (same result).  k_res (D, Lk2) fp32: the M2 residual long convolution, added in
+    the gated kernel's output epilogue."""
     if uc.dim() != 3 or uc.shape[1] % 3:
         raise RuntimeError("gated_conv_from_slices: uc must be (B, 3*D, L)")
     D, L = uc.shape[1] // 3, uc.shape[2]
+    if k_res is not None and (not torch.is_tensor(k_res) or k_res.dim() != 2 or k_res.shape[0] != D):
+        raise RuntimeError(f"gated_conv_from_slices: k_res must be (D = {D}, Lk)")
     # a model built for its longest sequence and run on a shorter one: the smallest fft size that holds the rows (FlashFFTConv._fit_seqlen)
-    n = conv._fit_seqlen(L, k.shape[-1]) if k.dim() == 2 else conv.seqlen
+    lk = k.shape[-1] if k_res is None or k.dim() != 2 else max(k.shape[-1], k_res.shape[-1])
+    n = conv._fit_seqlen(L, lk) if k.dim() == 2 else conv.seqlen
     if n != conv.seqlen:
         conv = conv._fitted_module(n)
     # (the strided launchers address one tensor with 31-bit element offsets: (B-1) * 3*D*L + D*L has to stay below 2^31,
     # where the composition on contiguous copies only needs B*D*L < 2^31)
     too_wide = (uc.shape[0] - 1) * 3 * D * L + D * L >= 2 ** 31
-    if conv._big or conv._route_big(max(L, k.shape[-1])) or conv._kf_keep is not None or (D * L) % 8 or not uc.is_contiguous() or too_wide:
+    if conv._big or conv._route_big(max(L, lk)) or conv._kf_keep is not None or (D * L) % 8 or not uc.is_contiguous() or too_wide:
         x1, x2, v = (t.contiguous() for t in uc.split(D, dim=1))
-        return conv(v, k, x1, x2)
+        return conv(v, k, x1, x2) if k_res is None else conv(v, k, x1, x2, residual=conv(v, k_res))
     _check_inputs(conv, uc[:, :D], k, ())
-    return _apply_noting_grad_mode(_GatedSlicesFn, uc, k, conv)
+    if k_res is not None:
+        _check_inputs(conv, uc[:, :D], k_res, ())
+    return _apply_noting_grad_mode(_GatedSlicesFn, uc, k, conv, k_res)
 
 
 class FlashHyenaOp(torch.nn.Module):
     """short depthwise conv (k = 3, "same" length) over the 3*D projected channels, then y = x2 * fftconv(x1 * v, k).
 
-    forward(x1x2v, k): x1x2v (B, 3*D, L) bf16/fp16 (the in-projection's output, channels first), k (D, Lk) fp32 -> (B, D, L).
+    forward(x1x2v, k, k_res=None): x1x2v (B, 3*D, L) bf16/fp16 (the in-projection's output, channels first), k (D, Lk) fp32 -> (B, D, L);
+    with k_res (D, Lk2) fp32, y = x2 * fftconv(x1 * v, k) + fftconv(v, k_res) (M2-BERT's residual_long_conv).
     `short_filter_weight` (3D, 1, 3) or (3D, 3) and `short_filter_bias` (3D,) are the nn.Conv1d parameters the reference
     callers pass to FlashDepthWiseConv1d (hyenadna_flashfftconv.py:248-261: padding=1, i.e. the [..., :l] crop is a no-op)."""
 
@@ -135,9 +188,9 @@ class FlashHyenaOp(torch.nn.Module):
                                                  device=device, dtype=dtype)
         self.flashfftconv = FlashFFTConv(fft_size, dtype=dtype)
 
-    def forward(self, x1x2v, k):
+    def forward(self, x1x2v, k, k_res=None):
         uc = self.short_filter(x1x2v)
-        return gated_conv_from_slices(self.flashfftconv, uc, k)
+        return gated_conv_from_slices(self.flashfftconv, uc, k, k_res)
 
 
 _LOOP_MAX_BATCH = 16
@@ -254,6 +307,6 @@ class FlashHyenaMixer(torch.nn.Module):
         self.in_proj, self.out_proj = in_proj, out_proj
         self.op = FlashHyenaOp(d_model, fft_size, short_filter_weight, short_filter_bias, dtype=dtype, device=device)
 
-    def forward(self, u, k):
-        y = self.op(project_in(self.in_proj.weight, u), k)
+    def forward(self, u, k, k_res=None):
+        y = self.op(project_in(self.in_proj.weight, u), k, k_res)
         return project_out(self.out_proj.weight, self.out_proj.bias, y)

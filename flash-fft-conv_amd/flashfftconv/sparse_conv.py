@@ -42,12 +42,13 @@ class _ConvCache(torch.nn.Module):
 class PartialFFTConv(_ConvCache):
     """reference flashfftconv/sparse_conv.py:8-22"""
 
-    def forward(self, x, k):
-        return self._conv_for(x)(x, k[..., : self.N_partial])
+    def forward(self, x, k, residual=None):
+        return self._conv_for(x)(x, k[..., : self.N_partial], residual=residual)
 
 
 class FrequencySparseFFTConv(_ConvCache):
     """reference flashfftconv/sparse_conv.py:24-38: rfft bins >= N_partial // 2 of k are zeroed."""
 
-    def forward(self, x, k):
-        return self._conv_for(x, keep=self.N_partial // 2)(x, k)
+    def forward(self, x, k, residual=None):
+        # (residual: FlashFFTConv.forward; on the compute-skipping kernel, fft 16384 / 32768 with N_partial <= fft / 4, it is added by composition)
+        return self._conv_for(x, keep=self.N_partial // 2)(x, k, residual=residual)

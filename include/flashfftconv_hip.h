@@ -106,6 +106,19 @@ int64_t ffc_spectrum_bytes(const ffc_plan* plan, int64_t B, int64_t H);
 int ffc_conv_fwd_z(const ffc_plan* plan, const void* u, const void* kf, const void* pregate, const void* postgate, void* y,
                    void* zsave, void* y_raw, int64_t B, int64_t H, int64_t L, int64_t sb_u, int64_t sb_pre, int64_t sb_post,
                    int64_t sb_y, void* stream);
+/* The forward with a residual input added in its output epilogue: y = postgate * conv(u * pregate, k) + addend, the product and the
+ * sum in fp32, rounded ONCE to the plan dtype (ungated: round(f32(conv) + f32(addend))).  A skip connection or a second branch -- the
+ * M2-BERT mixer's residual long convolution y = x2 * conv(x1 * v, k) + conv(v, k2), reference
+ * examples/bert/monarch_mixer_sequence_mixer_flashfftconv.py:151-175 -- costs one more row load in the kernel that already holds the
+ * output rows in registers, instead of an elementwise kernel behind it (2 reads + 1 write of a row tensor).  The superset of
+ * ffc_conv_fwd_strided and ffc_conv_fwd_z: addend (nullable: then exactly those calls) is addressed like postgate, sb_add its batch
+ * stride in elements (0 = contiguous); zsave / y_raw nullable under the rules of ffc_conv_fwd_z, and y_raw stays the output BEFORE gate
+ * and addend (dpostgate = dout * y_raw).  Every fused plan (fft 256 ... 131072).  Kernels of their own (csrc/ffc_k_conv_res.hip); the
+ * backward never sees the addend: its gradient is dout.  Returns an error without launching when addend overlaps y (the multi-pass
+ * sizes read-modify-write y between their passes). */
+int ffc_conv_fwd_res(const ffc_plan* plan, const void* u, const void* kf, const void* pregate, const void* postgate,
+                     const void* addend, void* y, void* zsave, void* y_raw, int64_t B, int64_t H, int64_t L, int conj_kf,
+                     int64_t sb_u, int64_t sb_pre, int64_t sb_post, int64_t sb_add, int64_t sb_y, void* stream);
 int ffc_conv_bwd_z(const ffc_plan* plan, const void* dout, const void* u, const void* kf, const void* pregate,
                    const void* postgate, void* du, void* dpre, void* dpost, void* ws, const void* zin, int64_t B, int64_t H,
                    int64_t L, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post, int64_t sb_du, int64_t sb_dpre,
