@@ -2,18 +2,22 @@
 #include "ffc_dev.h"
 using namespace ffc;
 
-template <int N0, int DT, bool FWD>
+// ST: batch-strided long side (BigBody's ST; BigArgs::strided picks it at launch)
+template <int N0, int DT, bool FWD, bool ST = false>
 __global__ __launch_bounds__(GeoBig<N0>::WGW * 64, 2) void big_kernel(BigArgs a) {
-  BigBody<DevB, N0, DT>::template run<FWD>(a, blockIdx.x);
+  BigBody<DevB, N0, DT, ST>::template run<FWD>(a, blockIdx.x);
 }
 
-template <int N0, int DT, bool FWD>
+template <int N0, int DT, bool FWD, bool ST = false>
 static int launch_big(const BigArgs& a, hipStream_t st) {
-  int rc = ffc_set_lds(big_kernel<N0, DT, FWD>, GeoBig<N0>::LDS_BYTES);
+  if constexpr (!ST) {
+    if (a.strided) return launch_big<N0, DT, FWD, true>(a, st);
+  }
+  int rc = ffc_set_lds(big_kernel<N0, DT, FWD, ST>, GeoBig<N0>::LDS_BYTES);
   if (rc) return rc;
   const int64_t nwg = (int64_t)a.npair * a.Hin * (a.Mi / GeoBig<N0>::Mi);
   if (nwg <= 0 || nwg > 2147483647LL) return ffc_fail("outer pass: bad grid");
-  hipLaunchKernelGGL((big_kernel<N0, DT, FWD>), dim3((unsigned)nwg), dim3(GeoBig<N0>::WGW * 64), GeoBig<N0>::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((big_kernel<N0, DT, FWD, ST>), dim3((unsigned)nwg), dim3(GeoBig<N0>::WGW * 64), GeoBig<N0>::LDS_BYTES, st, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : ffc_fail(std::string("big_kernel launch: ") + hipGetErrorString(e));
 }
@@ -41,9 +45,10 @@ static int launch_big_pipe(const BigArgs& a, int num_cu, hipStream_t st) {
 // 12.0 / 13.7 against 11.0 / 12.8, fft 1M 49.5 / 55.5 against 47.8 / 53.6 (a first version without the loader wave: 12.6 / 14.5).  Two
 // independent one-block workgroups per CU keep more of the HBM pipe busy than one workgroup that double-buffers.  Kept because the
 // GPU parity suite ran green on it and the next attempt (two pipelined workgroups of 32 KB blocks) starts from here.
+// A batch-strided long side (BigArgs::strided) never takes it: big_pipe_kernel has no ST = true build, such a call runs big_kernel<.., ST = true>.
 template <int N0, int DT, bool FWD>
 static int launch_level(const BigArgs& a, const ffc_plan* p, hipStream_t st) {
-  const bool pipe = a.R == 1 && a.fast && !a.lf32 && !a.half && !(FWD && a.gate) && (p->env_flags & 16);
+  const bool pipe = a.R == 1 && a.fast && !a.lf32 && !a.half && !a.strided && !(FWD && a.gate) && (p->env_flags & 16);
   return pipe ? launch_big_pipe<N0, DT, FWD>(a, p->num_cu, st) : launch_big<N0, DT, FWD>(a, st);
 }
 
@@ -59,12 +64,30 @@ static int decode_dtype(int dtype, int dir, BigArgs* a) {
   return dtype & 15;
 }
 
+// The long side of a level: batch pitches in elements (0 = contiguous, Hin * Llong) of `in` (dir = 1) / `out` (dir = 0) and of the gate, and
+// whether it takes 16-byte accesses: rows of a multiple of 8 elements, every base pointer 16-byte aligned, every pitch a multiple of 8.
+// Otherwise the element-wise path runs, as it does for odd Llong.  The short side is always contiguous: its pitch must be given as 0.
+static const char* set_long_side(BigArgs* a, int dir, int64_t Hin, int64_t Llong, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
+  const int64_t hl = Hin * Llong;
+  if ((dir ? pitch_out : pitch_in) != 0) return "outer pass: the short side (pair-plane tensor) is contiguous, its pitch must be 0";
+  int64_t pl = dir ? pitch_in : pitch_out, pg = a->gate ? pitch_gate : 0;
+  if (!pl) pl = hl;
+  if (!pg) pg = hl;
+  if (pl < hl || pg < hl) return "outer pass: a batch pitch is smaller than Hin * Llong";
+  if (a->lf32 && pl != hl) return "outer pass: the fp32 long side is contiguous";
+  a->pin = dir ? pl : 0; a->pout = dir ? 0 : pl; a->pgate = pg;
+  a->strided = (pl != hl || pg != hl) ? 1 : 0;
+  a->fast = (Llong % 8 == 0) && !(((uintptr_t)a->in | (uintptr_t)a->out | (uintptr_t)a->gate) & 15) && !((pl | pg) & 7);
+  return nullptr;
+}
+
 // One outer level.  dir = 1 forward (long side `in` (Bv,Hin,Llong) -> `out` (2*npair, Hin*N0, Mi)),
 // dir = 0 inverse (`in` (2*npair, Hin*N0, Mi) -> long side `out` (Bv,Hin,Llong)).
 // `plan` supplies the N0-point DFT operand table in `dtype` (any plan of a size whose outer digit is N0).
-extern "C" int ffc_outer_pass(const ffc_plan* plan16, const ffc_plan* plan32, int n0, int dtype, int dir, const void* in, void* out,
-                              const void* gate, int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale,
-                              void* stream) {
+// pitch_*: batch pitches of the long-side operands in elements, 0 = contiguous (set_long_side).
+extern "C" int ffc_outer_pass_strided(const ffc_plan* plan16, const ffc_plan* plan32, int n0, int dtype, int dir, const void* in, void* out,
+                                      const void* gate, int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale,
+                                      int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate, void* stream) {
   const ffc_plan* p = n0 == 16 ? plan16 : plan32;
   if (!p || !in || !out) return ffc_fail("null arg");
   if (n0 != p->hp.N1) return ffc_fail("outer pass: plan's outer digit does not match n0");
@@ -79,7 +102,7 @@ extern "C" int ffc_outer_pass(const ffc_plan* plan16, const ffc_plan* plan32, in
   a.fmat = (bf ? p->d_blob_bf : p->d_blob) + (bf ? p->hp_bf.tabs.mat[0] : p->hp.tabs.mat[0]);
   if (!bf && p->hp.dtype != DT_F16) return ffc_fail("outer pass: fp16 tables need an fp16 plan");
   a.Bp_valid = (int)Bv; a.npair = (int)npair; a.Hin = (int)Hin; a.Mi = (int)Mi; a.Llong = (int)Llong; a.scale = scale;
-  a.fast = (Llong % 8 == 0) && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gate) & 15);
+  if (const char* e = set_long_side(&a, dir, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return ffc_fail(e);
   a.R = 1; a.c = 0;
   hipStream_t st = (hipStream_t)stream;
   if (n0 == 16) {
@@ -89,6 +112,11 @@ extern "C" int ffc_outer_pass(const ffc_plan* plan16, const ffc_plan* plan32, in
   if (bf) return dir ? launch_level<32, DT_BF16, true>(a, p, st) : launch_level<32, DT_BF16, false>(a, p, st);
   return dir ? launch_level<32, DT_F16, true>(a, p, st) : launch_level<32, DT_F16, false>(a, p, st);
 }
+extern "C" int ffc_outer_pass(const ffc_plan* plan16, const ffc_plan* plan32, int n0, int dtype, int dir, const void* in, void* out,
+                              const void* gate, int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale,
+                              void* stream) {
+  return ffc_outer_pass_strided(plan16, plan32, n0, dtype, dir, in, out, gate, Bv, npair, Hin, Mi, Llong, scale, 0, 0, 0, stream);
+}
 
 // One level of factor R * 32 as R passes of the 32-point kernel (BigArgs::R): fft 4194304 = 128 x 32768 in ONE HBM level when
 // the long side is at most a quarter of it (Llong <= 32 * Mi, the HyenaDNA shape L = N / 4), instead of two levels of 16
@@ -97,8 +125,9 @@ extern "C" int ffc_outer_pass(const ffc_plan* plan16, const ffc_plan* plan32, in
 // its per-pass outer-digit tables are the matrices needed here.  dir = 1: every pass reads the long side and writes its
 // 32 rows of the R * 32 per head; dir = 0: pass c reads its rows, passes c > 0 add to the long side (call them in order).
 // An output gate (dir = 0) multiplies every pass's contribution before it is added: the same product, distributed over the sum.
-extern "C" int ffc_outer_pass_r(const ffc_plan* plan_r, int c, int dtype, int dir, const void* in, void* out, const void* gate,
-                                int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, void* stream) {
+extern "C" int ffc_outer_pass_r_strided(const ffc_plan* plan_r, int c, int dtype, int dir, const void* in, void* out, const void* gate,
+                                        int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale,
+                                        int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate, void* stream) {
   const ffc_plan* p = plan_r;
   if (!p || !in || !out) return ffc_fail("null arg");
   if (p->hp.N1 != 32 || p->hp.R < 2) return ffc_fail("outer pass (R passes): needs a multi-pass plan with a 32-point outer digit");
@@ -115,26 +144,33 @@ extern "C" int ffc_outer_pass_r(const ffc_plan* plan_r, int c, int dtype, int di
   if (!bf && p->hp.dtype != DT_F16) return ffc_fail("outer pass: fp16 tables need an fp16 plan");
   a.fmat = (bf ? p->d_blob_bf : p->d_blob) + (bf ? p->hp_bf.tabs.matk[c][dir ? 0 : 1] : p->hp.tabs.matk[c][dir ? 0 : 1]);
   a.Bp_valid = (int)Bv; a.npair = (int)npair; a.Hin = (int)Hin; a.Mi = (int)Mi; a.Llong = (int)Llong; a.scale = scale;
-  a.fast = (Llong % 8 == 0) && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gate) & 15);
+  if (const char* e = set_long_side(&a, dir, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return ffc_fail(e);
   a.R = R; a.c = c;
   hipStream_t st = (hipStream_t)stream;
   if (bf) return dir ? launch_big<32, DT_BF16, true>(a, st) : launch_big<32, DT_BF16, false>(a, st);
   return dir ? launch_big<32, DT_F16, true>(a, st) : launch_big<32, DT_F16, false>(a, st);
 }
+extern "C" int ffc_outer_pass_r(const ffc_plan* plan_r, int c, int dtype, int dir, const void* in, void* out, const void* gate,
+                                int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, void* stream) {
+  return ffc_outer_pass_r_strided(plan_r, c, dtype, dir, in, out, gate, Bv, npair, Hin, Mi, Llong, scale, 0, 0, 0, stream);
+}
 
 // ---- all R passes of a factor R * 32 in one launch (BigBody::run_all): the forward reads the long side once instead of R times,
 // the inverse sums the passes in its fp32 accumulators and writes the long side once (no read-modify-write between launches)
-template <int DT, bool FWD>
+template <int DT, bool FWD, bool ST = false>
 __global__ __launch_bounds__(GeoBig<32>::WGW * 64, 2) void big_all_kernel(BigArgs a) {
-  BigBody<DevB, 32, DT>::template run_all<FWD>(a, blockIdx.x);
+  BigBody<DevB, 32, DT, ST>::template run_all<FWD>(a, blockIdx.x);
 }
-template <int DT, bool FWD>
+template <int DT, bool FWD, bool ST = false>
 static int launch_big_all(const BigArgs& a, hipStream_t st) {
-  int rc = ffc_set_lds(big_all_kernel<DT, FWD>, GeoBig<32>::EBYTES);
+  if constexpr (!ST) {
+    if (a.strided) return launch_big_all<DT, FWD, true>(a, st);
+  }
+  int rc = ffc_set_lds(big_all_kernel<DT, FWD, ST>, GeoBig<32>::EBYTES);
   if (rc) return rc;
   const int64_t nwg = (int64_t)a.npair * a.Hin * (a.Mi / GeoBig<32>::Mi);
   if (nwg <= 0 || nwg > 2147483647LL) return ffc_fail("outer pass: bad grid");
-  hipLaunchKernelGGL((big_all_kernel<DT, FWD>), dim3((unsigned)nwg), dim3(GeoBig<32>::WGW * 64), GeoBig<32>::EBYTES, st, a);
+  hipLaunchKernelGGL((big_all_kernel<DT, FWD, ST>), dim3((unsigned)nwg), dim3(GeoBig<32>::WGW * 64), GeoBig<32>::EBYTES, st, a);
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? 0 : ffc_fail(std::string("big_all_kernel launch: ") + hipGetErrorString(e));
 }
@@ -156,8 +192,9 @@ static int launch_big_wide(const BigArgs& a, hipStream_t st) {
   return e == hipSuccess ? 0 : ffc_fail(std::string("big_wide_kernel launch: ") + hipGetErrorString(e));
 }
 // Same level as the R calls ffc_outer_pass_r(plan_r, c = 0 .. R-1, ...), in one launch.
-extern "C" int ffc_outer_pass_all(const ffc_plan* plan_r, int dtype, int dir, const void* in, void* out, const void* gate,
-                                  int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, void* stream) {
+extern "C" int ffc_outer_pass_all_strided(const ffc_plan* plan_r, int dtype, int dir, const void* in, void* out, const void* gate,
+                                          int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale,
+                                          int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate, void* stream) {
   const ffc_plan* p = plan_r;
   if (!p || !in || !out) return ffc_fail("null arg");
   if (p->hp.N1 != 32 || p->hp.R < 2 || p->hp.R > 4) return ffc_fail("outer pass (R passes): needs a multi-pass plan with a 32-point outer digit");
@@ -174,10 +211,11 @@ extern "C" int ffc_outer_pass_all(const ffc_plan* plan_r, int dtype, int dir, co
     a.fmats[c] = (bf ? p->d_blob_bf : p->d_blob) + (bf ? p->hp_bf.tabs.matk[c][dir ? 0 : 1] : p->hp.tabs.matk[c][dir ? 0 : 1]);
   a.fmat = a.fmats[0];
   a.Bp_valid = (int)Bv; a.npair = (int)npair; a.Hin = (int)Hin; a.Mi = (int)Mi; a.Llong = (int)Llong; a.scale = scale;
-  a.fast = (Llong % 8 == 0) && !(((uintptr_t)in | (uintptr_t)out | (uintptr_t)gate) & 15);
+  if (const char* e = set_long_side(&a, dir, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return ffc_fail(e);
   a.R = p->hp.R; a.c = 0;
   hipStream_t st = (hipStream_t)stream;
   if (Llong > 32 * Mi) {      // more than the first 32 long-side rows: the wide form
+    if (a.strided) return ffc_fail("outer pass (R passes), wide form: contiguous long side only");
     if (a.lf32 || a.half) return ffc_fail("outer pass (R passes), long side beyond the first 32 rows: 16-bit rows and all short-side rows only");
     if (GeoBig<32>::WGW % a.R) return ffc_fail("outer pass (R passes), wide form: R must divide the workgroup's waves");
     a.wide = 1;
@@ -186,4 +224,8 @@ extern "C" int ffc_outer_pass_all(const ffc_plan* plan_r, int dtype, int dir, co
   }
   if (bf) return dir ? launch_big_all<DT_BF16, true>(a, st) : launch_big_all<DT_BF16, false>(a, st);
   return dir ? launch_big_all<DT_F16, true>(a, st) : launch_big_all<DT_F16, false>(a, st);
+}
+extern "C" int ffc_outer_pass_all(const ffc_plan* plan_r, int dtype, int dir, const void* in, void* out, const void* gate,
+                                  int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, void* stream) {
+  return ffc_outer_pass_all_strided(plan_r, dtype, dir, in, out, gate, Bv, npair, Hin, Mi, Llong, scale, 0, 0, 0, stream);
 }

@@ -614,16 +614,42 @@ int ffcsim_conv_fwd_res(int N, int dtype, const void* u, const void* kf, const v
 }
 
 
+// the library's rule for the long side (ffc_k_big.hip set_long_side): batch pitches in elements, 0 = contiguous, of `in` (fwd) / `out` (inverse)
+// and of the gate; 16-byte accesses need rows of a multiple of 8, 16-byte aligned base pointers and pitches that are multiples of 8
+static int set_long_side(BigArgs* a, int fwd, int Hin, int Llong, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
+  const int64_t hl = (int64_t)Hin * Llong;
+  if ((fwd ? pitch_out : pitch_in) != 0) return -7;
+  int64_t pl = fwd ? pitch_in : pitch_out, pg = a->gate ? pitch_gate : 0;
+  const bool strided = pl || pg;
+  if (!pl) pl = hl;
+  if (!pg) pg = hl;
+  if (pl < hl || pg < hl || (a->lf32 && pl != hl)) return -7;
+  a->pin = fwd ? pl : 0; a->pout = fwd ? 0 : pl; a->pgate = pg;
+  a->strided = (pl != hl || pg != hl) ? 1 : 0;
+  a->fast = (Llong % 8 == 0) && !g_force_slow && !((pl | pg) & 7);
+  if (strided && (((uintptr_t)a->in | (uintptr_t)a->out | (uintptr_t)a->gate) & 15)) a->fast = 0;     // (the contiguous entry points keep taking any host pointer)
+  return 0;
+}
+
 // HBM-level outer pass (ffc_big.h).  fwd: in = long side (Bp_valid rows, Hin, Llong), out = (2*npair, Hin*N0, Mi).
+// *_strided: with the batch pitches of the long-side operands (ffc_outer_pass*_strided), on the same kernel body.
+int ffcsim_big_outer_r_strided(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
+                               int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate);
 int ffcsim_big_outer_r(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
-                       int Hin, int Mi, int Llong, float scale);
+                       int Hin, int Mi, int Llong, float scale) {
+  return ffcsim_big_outer_r_strided(N0, R, c, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, 0, 0, 0);
+}
 int ffcsim_big_outer(int N0, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
                      int Hin, int Mi, int Llong, float scale) {
   return ffcsim_big_outer_r(N0, 1, 0, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale);
 }
+int ffcsim_big_outer_strided(int N0, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
+                             int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
+  return ffcsim_big_outer_r_strided(N0, 1, 0, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, pitch_in, pitch_out, pitch_gate);
+}
 // R > 1: pass c of a factor R * 32 (ffc_outer_pass_r; tables of the R-pass plan of the fused 32768 kernel)
-int ffcsim_big_outer_r(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
-                       int Hin, int Mi, int Llong, float scale) {
+int ffcsim_big_outer_r_strided(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
+                               int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
   HostPlan p;
   if (R > 1 && N0 != 32) return -3;
   // the library's dtype flags (ffc_k_big.hip decode_dtype): | 16 = fp32 long side, bits 8..15 = log2 of the forward prescale
@@ -638,17 +664,18 @@ int ffcsim_big_outer_r(int N0, int R, int c, int dtype, int fwd, const void* in,
   a.lf32 = lf32; a.lpre = lpre; a.half = half;
   a.in = in; a.out = out; a.gate = gate; a.fmat = p.blob.data() + (R > 1 ? p.tabs.matk[c][fwd ? 0 : 1] : p.tabs.mat[0]);
   a.Bp_valid = Bp_valid; a.npair = npair; a.Hin = Hin; a.Mi = Mi; a.Llong = Llong; a.scale = scale;
-  a.fast = (Llong % 8 == 0) && !g_force_slow;
+  if (int rc = set_long_side(&a, fwd, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return rc;
   const int cols = N0 == 16 ? GeoBig<16>::Mi : GeoBig<32>::Mi;
   if (Mi % cols) return -2;
   const int nwg = npair * Hin * (Mi / cols);
   // the launcher's rule (ffc_k_big.hip launch_level): persistent double-buffered form for plain levels with 16-byte accesses and no
   // input gate; here 3 "workgroups" walk the blocks so that every one of them runs several iterations
-  const bool pipe = g_big_pipe && R == 1 && a.fast && !a.lf32 && !a.half && !(fwd && gate);
+  const bool pipe = g_big_pipe && R == 1 && a.fast && !a.lf32 && !a.half && !a.strided && !(fwd && gate);
   const int npw = pipe ? (nwg < 3 ? nwg : 3) : nwg;
   for (int wg = 0; wg < npw; wg++) {
 #define FFC_BIG(NN, DD, FF) run_wg(GeoBig<NN>::WGW + (pipe ? 1 : 0), pipe ? BigBody<SimB, NN, DD>::PIPE_LDS : GeoBig<NN>::LDS_BYTES, [&]() { \
-      if (pipe) BigBody<SimB, NN, DD>::template run_pipe<FF>(a, wg, npw); else BigBody<SimB, NN, DD>::template run<FF>(a, wg); })
+      if (pipe) BigBody<SimB, NN, DD>::template run_pipe<FF>(a, wg, npw); \
+      else if (a.strided) BigBody<SimB, NN, DD, true>::template run<FF>(a, wg); else BigBody<SimB, NN, DD>::template run<FF>(a, wg); })
     if (N0 == 16) { if (dtype == DT_BF16) { if (fwd) FFC_BIG(16, DT_BF16, true); else FFC_BIG(16, DT_BF16, false); }
                     else { if (fwd) FFC_BIG(16, DT_F16, true); else FFC_BIG(16, DT_F16, false); } }
     else { if (dtype == DT_BF16) { if (fwd) FFC_BIG(32, DT_BF16, true); else FFC_BIG(32, DT_BF16, false); }
@@ -659,8 +686,14 @@ int ffcsim_big_outer_r(int N0, int R, int c, int dtype, int fwd, const void* in,
 }
 
 // all R passes in one workgroup run (ffc_outer_pass_all, BigBody::run_all)
+int ffcsim_big_outer_all_strided(int R, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
+                                 int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate);
 int ffcsim_big_outer_all(int R, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
                          int Hin, int Mi, int Llong, float scale) {
+  return ffcsim_big_outer_all_strided(R, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, 0, 0, 0);
+}
+int ffcsim_big_outer_all_strided(int R, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
+                                 int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
   HostPlan p;
   const int lf32 = (dtype & 16) ? 1 : 0;
   const int half = (dtype & 32) ? 1 : 0;
@@ -675,11 +708,13 @@ int ffcsim_big_outer_all(int R, int dtype, int fwd, const void* in, void* out, c
   for (int c = 0; c < R; c++) a.fmats[c] = p.blob.data() + p.tabs.matk[c][fwd ? 0 : 1];
   a.fmat = a.fmats[0];
   a.Bp_valid = Bp_valid; a.npair = npair; a.Hin = Hin; a.Mi = Mi; a.Llong = Llong; a.scale = scale;
-  a.fast = (Llong % 8 == 0) && !g_force_slow;
+  if (Llong <= 0) return -5;
+  if (int rc = set_long_side(&a, fwd, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return rc;
   if (Mi % GeoBig<32>::Mi) return -2;
   if (Llong > R * 32 * Mi) return -5;
   if (Llong > 32 * Mi) {      // the wide form (ffc_outer_pass_all: long side beyond the first 32 rows, BigBody::run_wide)
     if (lf32 || half || GeoBig<32>::WGW % R) return -6;
+    if (pitch_in || pitch_out || pitch_gate) return -7;      // contiguous long side only, as in the library
     a.wide = 1;
     const int nw = npair * Hin * (Mi / (128 * (GeoBig<32>::WGW / R)));
     for (int wg = 0; wg < nw; wg++) {
@@ -692,7 +727,8 @@ int ffcsim_big_outer_all(int R, int dtype, int fwd, const void* in, void* out, c
   }
   const int nwg = npair * Hin * (Mi / GeoBig<32>::Mi);
   for (int wg = 0; wg < nwg; wg++) {
-#define FFC_BIGA(DD, FF) run_wg(GeoBig<32>::WGW, GeoBig<32>::LDS_BYTES, [&]() { BigBody<SimB, 32, DD>::template run_all<FF>(a, wg); })
+#define FFC_BIGA(DD, FF) run_wg(GeoBig<32>::WGW, GeoBig<32>::LDS_BYTES, [&]() { \
+      if (a.strided) BigBody<SimB, 32, DD, true>::template run_all<FF>(a, wg); else BigBody<SimB, 32, DD>::template run_all<FF>(a, wg); })
     if (dtype == DT_BF16) { if (fwd) FFC_BIGA(DT_BF16, true); else FFC_BIGA(DT_BF16, false); }
     else { if (fwd) FFC_BIGA(DT_F16, true); else FFC_BIGA(DT_F16, false); }
 #undef FFC_BIGA

@@ -52,6 +52,10 @@ def lib():
         L.ffc_outer_pass.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_vp]
         L.ffc_outer_pass_r.argtypes = [c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_vp]
         L.ffc_outer_pass_all.argtypes = [c_vp, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_vp]
+        # ... with the batch pitches (in, out, gate; elements, 0 = contiguous) of the long-side operands
+        L.ffc_outer_pass_strided.argtypes = L.ffc_outer_pass.argtypes[:-1] + [c_i64] * 3 + [c_vp]
+        L.ffc_outer_pass_r_strided.argtypes = L.ffc_outer_pass_r.argtypes[:-1] + [c_i64] * 3 + [c_vp]
+        L.ffc_outer_pass_all_strided.argtypes = L.ffc_outer_pass_all.argtypes[:-1] + [c_i64] * 3 + [c_vp]
         L.ffc_kernel_fft_c.argtypes = [c_vp, c_vp, c_i64, c_vp, c_f, c_vp]
         L.ffc_kernel_ifft_grad_c.argtypes = [c_vp, c_vp, c_i64, c_i64, c_vp, c_f, c_vp]
         L.ffc_kernel_ifft_grad_c_slabs.argtypes = [c_vp, c_vp, c_i64, c_i64, c_vp, c_f, c_vp]

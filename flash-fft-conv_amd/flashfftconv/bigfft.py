@@ -101,7 +101,9 @@ def inner_sfwd(M):
 
 def levels_forward(ops, dt, N, x, B_valid, H, L, gate=None, fac=None, lf32=None):
     """x: (B_valid, H, L) long-side tensor -> (2*npair, H*prod(N0), M) pair-plane tensor.  fac: choose(N, ...) (default: BIG_FACTORS).
-    lf32: x is fp32 (the filter k); the first level multiplies by this power of two and rounds to dt itself (ops.LONG_F32)."""
+    lf32: x is fp32 (the filter k); the first level multiplies by this power of two and rounds to dt itself (ops.LONG_F32).
+    x and gate (16-bit) may be batch-strided: stride(2) == 1, stride(1) == L, any stride(0) -- a channel slice of a wider tensor, which the
+    first level reads in place (ops.outer takes the pitches; the library's ffc_outer_pass*_strided)."""
     factors, M = fac or BIG_FACTORS[N]
     npair = (B_valid + 1) // 2
     Hx, nlev, Llong, bv = H, N, L, B_valid
@@ -118,7 +120,8 @@ def levels_forward(ops, dt, N, x, B_valid, H, L, gate=None, fac=None, lf32=None)
 
 def levels_inverse(ops, dt, N, y, out, B_valid, H, L, gate=None, shared=None, fac=None, lf32=False):
     """y: (2*npair, H*prod(N0), M) -> out (B_valid, H, L) (written in place).  `shared` caches the
-    intermediate of the two-level case so several gated outputs reuse it.  lf32: `out` is fp32 (dk), written by the last level."""
+    intermediate of the two-level case so several gated outputs reuse it.  lf32: `out` is fp32 (dk), written by the last level.
+    out and gate (16-bit) may be batch-strided like the long side of levels_forward: the last level writes the slice in place."""
     factors, M = fac or BIG_FACTORS[N]
     npair = y.shape[0] // 2
     Hx = H

@@ -129,9 +129,11 @@ def get_plan(seqlen, dtype, device):
 
 def reload_env():
     """tuning scripts: re-read FFC_* environment knobs into every cached plan (launches never read the environment)"""
+    global _ONE_LAUNCH_LEVEL
     for p in list(_PLANS.values()):
         _lib.lib().ffc_plan_reload_env(p.handle)
         p.__dict__.pop("_ws_cache", None)      # the workspace size depends on FFC_WG_MULT (chunks per head): ADVICE r04
+    _ONE_LAUNCH_LEVEL = _os.environ.get("FFC_BIG_ONE_LAUNCH", "1") != "0"      # the host-side switch of the levels of factor 64 / 128
 
 
 # Buffers the REFERENCE module registers (persistent, so they are in every checkpoint saved from it):
@@ -278,6 +280,21 @@ _BIG_ONE_CALL = _os.environ.get("FFC_BIG_ONE_CALL", "1") != "0"      # A/B switc
 _ONE_LAUNCH_LEVEL = _os.environ.get("FFC_BIG_ONE_LAUNCH", "1") != "0"      # A/B switch: "0" = one launch per pass (ffc_outer_pass_r)
 
 
+def _long_pitch(t, Hin, Llong):
+    """batch pitch in elements of a long-side tensor (B, Hin, Llong) of a level, 0 for a contiguous one (or none): the rows are dense
+    (stride(2) == 1, stride(1) == Llong), the batch stride is free -- a channel slice of a wider tensor (flashfftconv/hyena.py)"""
+    if t is None:
+        return 0
+    B, H, L = t.shape
+    if (H, L) != (Hin, Llong) or (L > 1 and t.stride(2) != 1) or (H > 1 and t.stride(1) != L):
+        raise RuntimeError(f"flashfftconv: a level's long side must be (B, {Hin}, {Llong}) with dense rows, got {tuple(t.shape)} strides {t.stride()}")
+    if B == 1 or t.stride(0) == H * L:
+        return 0
+    if t.stride(0) < H * L:
+        raise RuntimeError(f"flashfftconv: batch stride {t.stride(0)} of a level's long side is smaller than its rows ({H} x {L})")
+    return t.stride(0)
+
+
 class _TorchOps:
     """GPU backend of flashfftconv.bigfft (FFT sizes >= 65536): thin wrappers over the C-ABI."""
     BF16 = torch.bfloat16
@@ -315,10 +332,16 @@ class _TorchOps:
             assert 2.0 ** e == lf32 and (fwd or e == 0)
             assert (inp if fwd else out).dtype == torch.float32
             dcode |= 16 | (e << 8)
+        # batch-strided long side (read / written in place as a slice of a wider tensor): the *_strided entry points with the pitches of
+        # `in` (forward) / `out` (inverse) and of the gate; contiguous tensors keep the entry points without pitches
+        pl, pg = _long_pitch(inp if fwd else out, Hin, Llong), _long_pitch(gate, Hin, Llong)
+        pitches = ((pl, 0, pg) if fwd else (0, pl, pg)) if (pl or pg) else None
         if n0 in (64, 128):
             R = n0 // 32
             pr = self._plan(32768 * R)      # the R-pass plan: its per-pass outer-digit tables are the matrices of the passes
             if _big.is_wide(n0, mi, Llong):
+                if pitches:
+                    raise RuntimeError("flashfftconv: the wide form of a level takes contiguous tensors only")
                 # the wide form moves 16-bit rows: the fp32 filter is rounded in front of it (the product with its prescale, rounded once -- what the
                 # level's own fp32 load does) and the fp32 dk widened behind it (the level rounds its results to 16 bits before they leave LDS either way)
                 assert not self.half
@@ -331,14 +354,29 @@ class _TorchOps:
                     out.copy_(tmp)
                 return
             if _ONE_LAUNCH_LEVEL:       # all R passes in one launch (long side read / written once)
+                if pitches:
+                    _lib.check(_lib.lib().ffc_outer_pass_all_strided(pr.handle, dcode, int(fwd), _lib.ptr(inp), _lib.ptr(out), _lib.ptr(gate), bv,
+                                                                     npair, Hin, mi, Llong, ctypes.c_float(scale), *pitches, _lib.stream_ptr()),
+                               "ffc_outer_pass_all_strided")
+                    return
                 _lib.check(_lib.lib().ffc_outer_pass_all(pr.handle, dcode, int(fwd), _lib.ptr(inp), _lib.ptr(out), _lib.ptr(gate), bv,
                                                          npair, Hin, mi, Llong, ctypes.c_float(scale), _lib.stream_ptr()), "ffc_outer_pass_all")
                 return
             for c in range(R):
+                if pitches:
+                    _lib.check(_lib.lib().ffc_outer_pass_r_strided(pr.handle, c, dcode, int(fwd), _lib.ptr(inp), _lib.ptr(out), _lib.ptr(gate), bv,
+                                                                   npair, Hin, mi, Llong, ctypes.c_float(scale), *pitches, _lib.stream_ptr()),
+                               "ffc_outer_pass_r_strided")
+                    continue
                 _lib.check(_lib.lib().ffc_outer_pass_r(pr.handle, c, dcode, int(fwd), _lib.ptr(inp), _lib.ptr(out), _lib.ptr(gate), bv,
                                                        npair, Hin, mi, Llong, ctypes.c_float(scale), _lib.stream_ptr()), "ffc_outer_pass_r")
             return
         p16, p32 = self._plan(16384), self._plan(32768)
+        if pitches:
+            _lib.check(_lib.lib().ffc_outer_pass_strided(p16.handle, p32.handle, n0, dcode, int(fwd), _lib.ptr(inp), _lib.ptr(out),
+                                                         _lib.ptr(gate), bv, npair, Hin, mi, Llong, ctypes.c_float(scale), *pitches,
+                                                         _lib.stream_ptr()), "ffc_outer_pass_strided")
+            return
         _lib.check(_lib.lib().ffc_outer_pass(p16.handle, p32.handle, n0, dcode, int(fwd), _lib.ptr(inp), _lib.ptr(out),
                                              _lib.ptr(gate), bv, npair, Hin, mi, Llong, ctypes.c_float(scale),
                                              _lib.stream_ptr()), "ffc_outer_pass")
@@ -473,8 +511,10 @@ def _big_half(mod, B, Lmax, fac):
     return _BIG_HALF and B == 1 and mod._kf_keep is None
 
 
-def _big_forward(mod, u, k, pregate, postgate, keep=False, kf=None, fac=None, half=False):
-    """keep (training, module.save_spectrum): also return what the backward pass would otherwise compute again -- the
+def _big_forward(mod, u, k, pregate, postgate, keep=False, kf=None, fac=None, half=False, out=None):
+    """u, pregate, postgate and `out` (the result's tensor, allocated here when None) may be batch-strided (_long_pitch): the first forward
+    level and the last inverse level read / write them in place.
+    keep (training, module.save_spectrum): also return what the backward pass would otherwise compute again -- the
     transformed input x of the inner size (pair-plane rows), the inner spectra z (inner plans with that path) and, for the
     gated form, the inner output y (dpostgate = its inverse levels * dout).  kf: inner k_f rows computed elsewhere
     (_big_kernel_fft; the B-shard gathers them from the ranks), k is then unused."""
@@ -500,7 +540,8 @@ def _big_forward(mod, u, k, pregate, postgate, keep=False, kf=None, fac=None, ha
             y, z = ops.conv_save(dt, M, x, kf)
         else:
             y = ops.conv(dt, M, x, kf, False)
-    out = torch.empty_like(u)
+    if out is None:
+        out = torch.empty_like(u, memory_format=torch.contiguous_format)
     _big.levels_inverse(ops, dt, N, y, out, B, H, L, postgate, None, fac)
     # kept for the backward pass: the inner spectra z; the inner input rows x only when there are no spectra (the saved-spectra inner
     # kernel never reads them: round 5, a third of the kept bytes less); gated: the inner output y
@@ -517,8 +558,9 @@ def _big_dk_from_dkf(mod, dkf, k_len, fac=None):
     return _big.dk_from_slabs(ops, mod.seqlen, dkf.contiguous(), 2, h, k_len, nslab=1, fac=fac)
 
 
-def _big_backward(mod, dout, u, kf, pregate, postgate, k_len, kept=None, want_dkf=False, fac=None, half=False):
-    """want_dkf: return the fp32 inner dk_f rows summed over the local batch (hp, kf_elems, 2) instead of dk (B-shard: the
+def _big_backward(mod, dout, u, kf, pregate, postgate, k_len, kept=None, want_dkf=False, fac=None, half=False, outs=None):
+    """outs: (du, dpregate, dpostgate) tensors to write the gradients into (batch-strided ones are written in place; None: allocated here).
+    want_dkf: return the fp32 inner dk_f rows summed over the local batch (hp, kf_elems, 2) instead of dk (B-shard: the
     ranks reduce-scatter them and invert their own heads, _big_dk_from_dkf)"""
     N, dt = mod.seqlen, mod.dtype
     ops = _TorchOps(mod, u.device, half)
@@ -537,7 +579,7 @@ def _big_backward(mod, dout, u, kf, pregate, postgate, k_len, kept=None, want_dk
         # one call: the fused inner backward + the inner dk_f -> complex rows step (out of the same launch where a workgroup owns its row)
         yd, ypair = ops.bwd_dk(dt, M, xd, xu, kf, z, _big.dk_pair_scale(N, fac))      # (xu None: spectra kept)
         dk = _big.dk_from_pair(ops, N, ypair, H, k_len, fac)
-        return _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac)
+        return _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac, outs)
     yd, ws = ops.bwd(dt, M, xd, xu, kf, z)
     if xu is None:
         xu = xd          # (shape only, below)
@@ -556,23 +598,50 @@ def _big_backward(mod, dout, u, kf, pregate, postgate, k_len, kept=None, want_dk
         dk = slabs[0] if nslab == 1 else slabs.sum(0)
     else:
         dk = _big.dk_from_slabs(ops, N, ws, xu.shape[0], H, k_len, None, fac)
-    return _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac)
+    return _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac, outs)
 
 
-def _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac):
-    """the inverse levels of the gradients: du (* pregate), and for the gated form dpregate, dpostgate"""
-    du = torch.empty_like(u)
+def _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac, outs=None):
+    """the inverse levels of the gradients: du (* pregate), and for the gated form dpregate, dpostgate -- into `outs` when given"""
+    du, dpre, dpost = outs if outs is not None else (None, None, None)
+    if du is None:
+        du = torch.empty_like(u, memory_format=torch.contiguous_format)
     shared = {}
     _big.levels_inverse(ops, dt, N, yd, du, B, H, L, pregate, shared, fac)
     if pregate is None:
         return du, dk, None, None
-    dpre = torch.empty_like(u)
+    if dpre is None:
+        dpre = torch.empty_like(u, memory_format=torch.contiguous_format)
     _big.levels_inverse(ops, dt, N, yd, dpre, B, H, L, u, shared, fac)
     if yu is None:
         yu = ops.conv(dt, M, xu, kf, False)
-    dpost = torch.empty_like(u)
+    if dpost is None:
+        dpost = torch.empty_like(u, memory_format=torch.contiguous_format)
     _big.levels_inverse(ops, dt, N, yu, dpost, B, H, L, dout, None, fac)
     return du, dk, dpre, dpost
+
+
+def _big_forward_routed(mod, u, k, pregate, postgate, wants_grad, out=None):
+    """One forward call of an HBM-level route as the module runs it: what to keep for the backward (spectra within the memory budget), the
+    factorisation for these lengths, half rows or not -> (out, kf, kept, fac, half).  Shared by FlashFFTConv and the fused operator, which
+    passes batch-strided slices and its own `out` (flashfftconv/hyena.py)."""
+    gated = pregate is not None
+    keep = mod.training and mod.save_spectrum and _recording() and wants_grad
+    if keep:      # kept: the inner spectra z (4 B per point and pair), gated also the inner output y (4 B)
+        keep = _spectrum_budget_ok(((u.shape[0] + 1) // 2) * u.shape[1] * mod.seqlen * (8 if gated else 4), u.device, mod.save_spectrum)
+        if not keep:
+            SPECTRUM_FALLBACKS["budget"] += 1
+    # the factorisation may depend on the lengths (fft 4M: one level of 128 when everything fits a quarter of it)
+    fac = _big.choose(mod.seqlen, max(u.shape[-1], k.shape[-1]), _TorchOps)
+    half = _big_half(mod, u.shape[0], max(u.shape[-1], k.shape[-1]), fac)
+    try:
+        out, kf, kept = _big_forward(mod, u, k, pregate, postgate, keep, None, fac, half, out)
+    except torch.cuda.OutOfMemoryError:
+        if not keep:
+            raise
+        SPECTRUM_FALLBACKS["oom"] += 1
+        out, kf, kept = _big_forward(mod, u, k, pregate, postgate, False, None, fac, half, out)
+    return out, kf, kept, fac, half
 
 
 def _check_inputs(mod, u, k, gates):
@@ -628,21 +697,7 @@ class _FlashFFTConvFn(torch.autograd.Function):
         ctx.big = mod._big or mod._route_big(max(u.shape[-1], k.shape[-1]))
         kept = None
         if ctx.big:
-            keep = mod.training and mod.save_spectrum and _recording() and any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4))
-            if keep:      # kept: the inner spectra z (4 B per point and pair), gated also the inner output y (4 B)
-                keep = _spectrum_budget_ok(((u.shape[0] + 1) // 2) * u.shape[1] * mod.seqlen * (8 if ctx.gated else 4), u.device, mod.save_spectrum)
-                if not keep:
-                    SPECTRUM_FALLBACKS["budget"] += 1
-            # the factorisation may depend on the lengths (fft 4M: one level of 128 when everything fits a quarter of it)
-            ctx.fac = fac = _big.choose(mod.seqlen, max(u.shape[-1], k.shape[-1]), _TorchOps)
-            ctx.half = half = _big_half(mod, u.shape[0], max(u.shape[-1], k.shape[-1]), fac)
-            try:
-                out, kf, kept = _big_forward(mod, u, k, pregate, postgate, keep, None, fac, half)
-            except torch.cuda.OutOfMemoryError:
-                if not keep:
-                    raise
-                SPECTRUM_FALLBACKS["oom"] += 1
-                out, kf, kept = _big_forward(mod, u, k, pregate, postgate, False, None, fac, half)
+            out, kf, kept, ctx.fac, ctx.half = _big_forward_routed(mod, u, k, pregate, postgate, any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4)))
         else:
             plan = mod._get_plan(u.device, mod._plan_seqlen)
             kf = mod._cached_kf(k) if mod.cache_kf and not k.requires_grad else None

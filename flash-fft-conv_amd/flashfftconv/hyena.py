@@ -15,13 +15,19 @@ input, x1 the pregate, x2 the postgate, so the multiply kernels, the copy and th
 and in the backward (du / dpregate / dpostgate are written straight into the slices of d(uc), one launch; then the short
 convolution's own backward).  y = x2 * conv(x1 * v, k): the same function as the reference composition.
 
+The HBM-level routes (fft >= 262144, and fft 131072 with rows longer than half of it: flashfftconv/bigfft.py) do the same through the
+batch pitches of their level kernels (ffc_outer_pass*_strided): the first forward level of every transform reads v, x1, x2 (and, in the
+backward, writes du, dpregate, dpostgate through the last inverse level) as slices of uc / d(uc) -- _GatedSlicesBigFn.
+
 With k_res (the M2 residual long convolution, monarch_mixer_sequence_mixer_flashfftconv.py:151-175) y = x2 * conv(x1 * v, k) +
 conv(v, k_res) in two launches: conv(v, k_res) reading the v slice in place, then the gated kernel with that result as the addend of its
 output epilogue (ffc_conv_fwd_res) -- no copy of v and no add kernel."""
 import torch
 
 from . import _lib
-from .conv import FlashFFTConv, _check_inputs, _kernel_fft, _periodise_k, _spectrum_buffer, _kf_key, _apply_noting_grad_mode, _recording
+from .conv import (FlashFFTConv, _check_inputs, _kernel_fft, _periodise_k, _spectrum_buffer, _kf_key, _apply_noting_grad_mode, _recording,
+                   _big_forward_routed, _big_backward, _dev_ctx, _TorchOps)
+from . import bigfft as _bigfft
 from .depthwise_1d import FlashDepthWiseConv1d
 
 
@@ -146,11 +152,79 @@ class _GatedSlicesFn(torch.autograd.Function):
         return duc, dk.to(ctx.k_dtype), None, dk_res
 
 
+class _GatedSlicesBigFn(torch.autograd.Function):
+    """_GatedSlicesFn on the HBM-level routes: the module's own forward / backward of these sizes (conv._big_forward / _big_backward: levels,
+    inner kernel, what is kept for the backward) with v, x1, x2 passed as VIEWS of uc and du, dpregate, dpostgate as views of one
+    duc = empty_like(uc) -- the levels address them through their batch pitch.  Same kernels and arithmetic as the module called on
+    contiguous copies, so the same bits.  With k_res, conv(v, k_res) is a second (ungated) call on the v view whose result is added by
+    composition, as the module does at these sizes (no fused epilogue in the last inverse level); its input gradient is added into v's
+    slice of duc."""
+
+    @staticmethod
+    def forward(ctx, uc, k, mod, k_res=None):
+        B, D3, L = uc.shape
+        D = D3 // 3
+        x1, x2, v = uc[:, :D], uc[:, D:2 * D], uc[:, 2 * D:]
+        with _dev_ctx(uc.device):
+            y = torch.empty(B, D, L, dtype=uc.dtype, device=uc.device)
+            _, kf, kept, fac, half = _big_forward_routed(mod, v, k, x1, x2, any(ctx.needs_input_grad[:2]), y)
+            res = None
+            if k_res is not None:
+                yr, kf_r, kept_r, fac_r, half_r = _big_forward_routed(mod, v, k_res, None, None, ctx.needs_input_grad[0] or ctx.needs_input_grad[3])
+                y = y + yr
+                res = (kf_r, kept_r, fac_r, half_r, k_res.shape[-1], k_res.dtype)
+        ctx.mod, ctx.k_len, ctx.k_dtype, ctx.fac, ctx.half = mod, k.shape[-1], k.dtype, fac, half
+        ctx.layouts = ctx.res = None
+        if mod.training:
+            saved, layouts = [uc], []
+            for kf_, kept_ in ((kf, kept),) + (() if res is None else (res[:2],)):
+                layouts.append(None if kept_ is None else tuple(t is not None for t in kept_))
+                saved += [kf_] + ([] if kept_ is None else [t for t in kept_ if t is not None])
+            ctx.layouts = layouts
+            ctx.res = None if res is None else res[2:]
+            ctx.save_for_backward(*saved)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        if not ctx.saved_tensors:
+            raise RuntimeError("FlashHyenaOp: backward needs module.training=True at forward time")
+        it = iter(ctx.saved_tensors)
+        uc = next(it)
+        calls = []
+        for layout in ctx.layouts:
+            kf = next(it)
+            calls.append((kf, None if layout is None else tuple(next(it) if present else None for present in layout)))
+        mod = ctx.mod
+        B, D3, L = uc.shape
+        D = D3 // 3
+        x1, x2, v = uc[:, :D], uc[:, D:2 * D], uc[:, 2 * D:]
+        with _dev_ctx(uc.device):
+            dy = dy.contiguous()
+            duc = torch.empty_like(uc)
+            # u = v (slice 2), pregate = x1 (slice 0), postgate = x2 (slice 1); gradients land in the same slices of duc
+            outs = (duc[:, 2 * D:], duc[:, :D], duc[:, D:2 * D])
+            _, dk, _, _ = _big_backward(mod, dy, v, calls[0][0], x1, x2, ctx.k_len, calls[0][1], False, ctx.fac, ctx.half, outs)
+            dk_res = None
+            if ctx.res is not None:
+                fac_r, half_r, kr_len, kr_dtype = ctx.res
+                dv, dk_res, _, _ = _big_backward(mod, dy, v, calls[1][0], None, None, kr_len, calls[1][1], False, fac_r, half_r)
+                dk_res = dk_res.to(kr_dtype)
+                duc[:, 2 * D:].add_(dv)
+        return duc, dk.to(ctx.k_dtype), None, dk_res
+
+
 def gated_conv_from_slices(conv, uc, k, k_res=None):
     """y = x2 * conv(x1 * v, k) [+ conv(v, k_res)] with (x1, x2, v) = uc.split(D, dim=1), uc (B, 3D, L) contiguous, through `conv`
-    (a FlashFFTConv).  Sizes served by the fused kernels (fft <= 131072) read the slices in place; larger ones fall back to
-    the module's gated call on contiguous copies (same result).  k_res (D, Lk2) fp32: the M2 residual long convolution, added in
-    the gated kernel's output epilogue."""
+    (a FlashFFTConv).  Every route reads the slices in place and writes the gradients into the slices of one d(uc): the fused kernels
+    (fft <= 131072) through their strided launchers, the HBM-level routes (fft >= 262144, fft 131072 with rows longer than half of it)
+    through the batch pitches of their level kernels, at any L (odd L: element-wise accesses).  Contiguous copies of the slices and the
+    module's gated call (same result) remain for the frequency-sparse modules, the wide form of a level (FFC_BIG_WIDE=1), a
+    non-contiguous uc and uc.numel() >= 2^31.  k_res (D, Lk2) fp32: the M2 residual long convolution, added in the gated kernel's
+    output epilogue on the fused routes and by composition (a second convolution reading v in place, one add) on the HBM-level ones.
+    Both convolutions run on ONE module, fitted to the longer of the two filters (_fit_seqlen); the composition conv(v, k, x1, x2,
+    residual=conv(v, k_res)) fits each call to its own filter.  Nothing wraps at either size, so the results agree to rounding; they are the
+    same bits when both filters select the same fft size."""
     if uc.dim() != 3 or uc.shape[1] % 3:
         raise RuntimeError("gated_conv_from_slices: uc must be (B, 3*D, L)")
     D, L = uc.shape[1] // 3, uc.shape[2]
@@ -164,13 +238,27 @@ def gated_conv_from_slices(conv, uc, k, k_res=None):
     # (the strided launchers address one tensor with 31-bit element offsets: (B-1) * 3*D*L + D*L has to stay below 2^31,
     # where the composition on contiguous copies only needs B*D*L < 2^31)
     too_wide = (uc.shape[0] - 1) * 3 * D * L + D * L >= 2 ** 31
-    if conv._big or conv._route_big(max(L, lk)) or conv._kf_keep is not None or (D * L) % 8 or not uc.is_contiguous() or too_wide:
+    # HBM-level route or fused route: decided per filter by its own length, as the module does for conv(v, k) and conv(v, k_res)
+    lks = (k.shape[-1],) + (() if k_res is None else (k_res.shape[-1],))
+    bigs = [k.dim() == 2 and bool(conv._big or conv._route_big(max(L, lkx))) for lkx in lks]
+    big = all(bigs)
+    if big:
+        # the level routes: no (D * L) % 8 condition (unaligned slices take the element-wise path); not the wide form of a level
+        fit = conv._kf_keep is None and uc.is_contiguous() and uc.numel() < 2 ** 31
+        for lkx in lks:
+            factors, _ = _bigfft.choose(conv.seqlen, max(L, lkx), _TorchOps)
+            fit = fit and not _bigfft.is_wide(factors[0], conv.seqlen // factors[0], max(L, lkx))
+    elif any(bigs):
+        fit = False      # (fft 131072 with one filter routed by length and one not: the composition on copies)
+    else:
+        fit = not conv._big and conv._kf_keep is None and (D * L) % 8 == 0 and uc.is_contiguous() and not too_wide
+    if not fit:
         x1, x2, v = (t.contiguous() for t in uc.split(D, dim=1))
         return conv(v, k, x1, x2) if k_res is None else conv(v, k, x1, x2, residual=conv(v, k_res))
     _check_inputs(conv, uc[:, :D], k, ())
     if k_res is not None:
         _check_inputs(conv, uc[:, :D], k_res, ())
-    return _apply_noting_grad_mode(_GatedSlicesFn, uc, k, conv, k_res)
+    return _apply_noting_grad_mode(_GatedSlicesBigFn if big else _GatedSlicesFn, uc, k, conv, k_res)
 
 
 class FlashHyenaOp(torch.nn.Module):

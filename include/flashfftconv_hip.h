@@ -191,6 +191,24 @@ int ffc_outer_pass_r(const ffc_plan* plan_r, int c, int dtype, int dir, const vo
  * less peak memory: the module takes it on request (FFC_BIG_WIDE=1). */
 int ffc_outer_pass_all(const ffc_plan* plan_r, int dtype, int dir, const void* in, void* out, const void* gate, int64_t Bv,
                        int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, void* stream);
+/* The three level entry points on BATCH-STRIDED long-side tensors: a level reads / writes a channel slice of a wider tensor in place (the
+ * fused Hyena / M2 operator, flashfftconv/hyena.py: x1, x2, v as slices of uc (B, 3D, L), the gradients as slices of d(uc)) -- the
+ * counterpart of the *_strided launchers of the fused kernels for fft >= 262144.  pitch_in / pitch_out / pitch_gate: batch pitch in
+ * ELEMENTS of `in`, `out` and `gate`; row (b, h) of an operand starts at b * pitch + h * Llong (rows stay dense: stride(1) == Llong,
+ * stride(2) == 1).  0 = contiguous (Hin * Llong); a pitch below Hin * Llong is an error.  Only the long side has a pitch: the
+ * pair-plane tensor (`out` for dir = 1, `in` for dir = 0) is contiguous and its pitch must be 0, and so is a fp32 long side (| 16).
+ * 16-byte accesses need Llong % 8 == 0, every long-side base pointer 16-byte aligned and every pitch a multiple of 8; otherwise the
+ * element-wise path runs, as it does for odd Llong.  The wide form of ffc_outer_pass_all (Llong > 32 * Mi) takes contiguous tensors only.
+ * The entry points without pitches above are these with (0, 0, 0). */
+int ffc_outer_pass_strided(const ffc_plan* plan16, const ffc_plan* plan32, int n0, int dtype, int dir, const void* in, void* out,
+                           const void* gate, int64_t Bv, int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale,
+                           int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate, void* stream);
+int ffc_outer_pass_r_strided(const ffc_plan* plan_r, int c, int dtype, int dir, const void* in, void* out, const void* gate, int64_t Bv,
+                             int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, int64_t pitch_in, int64_t pitch_out,
+                             int64_t pitch_gate, void* stream);
+int ffc_outer_pass_all_strided(const ffc_plan* plan_r, int dtype, int dir, const void* in, void* out, const void* gate, int64_t Bv,
+                               int64_t npair, int64_t Hin, int64_t Mi, int64_t Llong, float scale, int64_t pitch_in, int64_t pitch_out,
+                               int64_t pitch_gate, void* stream);
 int ffc_kernel_fft_c(const ffc_plan* plan, const void* xpair, int64_t H, void* kf_out, float scale, void* stream);
 int ffc_kernel_ifft_grad_c(const ffc_plan* plan, const void* ws, int64_t B, int64_t H, void* outpair, float scale, void* stream);
 /* ... from `nslab` caller-owned fp32 slabs [nslab][H][kf_elems][2] (multi-GPU B-shard: rows reduce-scattered over the ranks) */
