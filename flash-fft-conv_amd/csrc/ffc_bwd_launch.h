@@ -56,66 +56,32 @@ __global__ __launch_bounds__(GEO::WGW * 64, 2) __attribute__((amdgpu_num_vgpr(12
 #pragma unroll 1
   for (int k0 = 0; k0 < d.c.R; k0++) Modes<BK, GEO, DT>::template bwd<HALF, true, true, ZM>(d, h, chunk, wg, k0, wv);
 }
-template <class K>
-static int ffc_bwd_rp_go(K kernel, int lds, dim3 grid, dim3 block, hipStream_t st, const DkfArgs& d) {
-  int rc = ffc_set_lds(kernel, lds);
-  if (rc) return rc;
-  hipLaunchKernelGGL(kernel, grid, block, lds, st, d);
-  return 0;
-}
 
+// the variant, grid and LDS rules are ffc::bwd_route (ffc_route.h)
 template <int ZM>
 struct BwdLaunchZ {
 template <class GEO, int DT>
 struct T {
   static int run(const DkfArgs& d, hipStream_t st) {
-    int hpad = (d.c.H + 7) & ~7;
-    int ngrid = hpad * d.c.nchunk;
-    if (d.c.R > 1) {
-      if constexpr (GEO::N == 32768) {
-        const dim3 grid(ngrid), block(GEO::WGW * 64);
-        const bool half = 16 * GEO::Mi >= d.c.L;
-        int rc;
-        if (d.c.fast && (FFC_RP_FASTK != 0)) rc = half ? ffc_bwd_rp_go(bwd_rp_kernel<GEO, DT, true, ZM, true>, GEO::LDS_BYTES, grid, block, st, d)
-                                : ffc_bwd_rp_go(bwd_rp_kernel<GEO, DT, false, ZM, true>, GEO::LDS_BYTES, grid, block, st, d);
-        else rc = half ? ffc_bwd_rp_go(bwd_rp_kernel<GEO, DT, true, ZM, false>, GEO::LDS_BYTES, grid, block, st, d)
-                       : ffc_bwd_rp_go(bwd_rp_kernel<GEO, DT, false, ZM, false>, GEO::LDS_BYTES, grid, block, st, d);
-        if (rc) return rc;
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("bwd_rp_kernel launch: ") + hipGetErrorString(e));
-      } else if constexpr (GEO::OUTER) {
-        return ffc_fail("multi-pass plan on a geometry without multi-pass kernels");
-      }
-    }
-    if (GEO::OUTER && GEO::NW == 1 && d.c.persist > 0 && ngrid > d.c.persist) ngrid = d.c.persist;   // persistent: one per CU
-    const dim3 grid(ngrid), block(GEO::WGW * 64);
+    static_assert(Body<DevB, GEO, DT>::IPASS_BYTES == IPASS_BYTES, "ffc_route.h");
+    const BwdRoute r = bwd_route<GEO>(d, false);
+    if (r.err) return ffc_fail(r.err);
+    constexpr int T_ = GEO::WGW * 64;
     if constexpr (!GEO::OUTER && ZM != 0) {
       return ffc_fail("single-tile sizes are launched by the recomputing unit (run-time spectrum switch)");
     } else if constexpr (!GEO::OUTER) {
-      using BD = Body<DevB, GEO, DT>;
-      const int lds = GEO::LDS_BYTES + (d.c.R > 1 ? d.c.R * BD::IPASS_BYTES : 0);
-      int rc = ffc_set_lds(bwd_kernel_small<GEO, DT>, GEO::LDS_BYTES + 2 * BD::IPASS_BYTES);
-      if (rc) return rc;
-      if (d.c.R > 1 && GEO::N != 1024) return ffc_fail("multi-pass plan on a geometry without multi-pass kernels");
-      const int cap = (d.c.persist > 0 && d.c.persist < (1 << 29)) ? 2 * d.c.persist : (1 << 30);      // FFC_PERSIST=0: uncapped
-      hipLaunchKernelGGL((bwd_kernel_small<GEO, DT>), dim3(ngrid > cap ? cap : ngrid), block, lds, st, d);
+      return ffc_launch(bwd_kernel_small<GEO, DT>, "bwd_kernel", r.grid, T_, r.lds_max, r.lds, st, d);
     } else {
-      const bool half = (GEO::N1 / 2) * GEO::Mi >= d.c.L;
-      if (half) {
-        {
-          int rc = ffc_set_lds(bwd_kernel<GEO, DT, true, ZM>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((bwd_kernel<GEO, DT, true, ZM>), grid, block, GEO::LDS_BYTES, st, d);
-        }
-      } else {
-        int rc = ffc_set_lds(bwd_kernel<GEO, DT, false, ZM>, GEO::LDS_BYTES);
-        if (rc) return rc;
-        hipLaunchKernelGGL((bwd_kernel<GEO, DT, false, ZM>), grid, block, GEO::LDS_BYTES, st, d);
-      }
+      return pick([&](auto mp, auto half, auto fastk) -> int {
+        constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value, FASTK = decltype(fastk)::value;
+        if constexpr (MP && GEO::N == 32768)
+          return ffc_launch(bwd_rp_kernel<GEO, DT, HALF, ZM, FASTK>, "bwd_rp_kernel", r.grid, T_, r.lds_max, r.lds, st, d);
+        else if constexpr (!MP && !FASTK)
+          return ffc_launch(bwd_kernel<GEO, DT, HALF, ZM>, "bwd_kernel", r.grid, T_, r.lds_max, r.lds, st, d);
+        else
+          return ffc_fail("internal: the backward route names a kernel that does not exist");
+      }, r.multi_pass, r.half, r.fastk);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : ffc_fail(std::string("bwd_kernel launch: ") + hipGetErrorString(e));
   }
 };
 };
-

@@ -13,6 +13,7 @@
 #include "ffc_body.h"
 #include "ffc_modes.h"
 #include "ffc_big.h"
+#include "ffc_route.h"
 
 namespace ffc {
 
@@ -330,35 +331,29 @@ int ffc_bwdz_launch(int N, int dtype, const ffc::DkfArgs& d, hipStream_t st);   
 template <class K>
 static int ffc_set_lds(K kernel, int bytes) { return ffc_set_lds_once((const void*)kernel, bytes); }
 
+// The launch triple: dynamic-LDS limit of the kernel, launch, launch error (`what` names the kernel in the message, which is built on the
+// failure path only).
+template <class K, class A>
+static int ffc_launch(K kernel, const char* what, dim3 grid, dim3 block, int lds_max, int lds, hipStream_t st, const A& args) {
+  if (int rc = ffc_set_lds(kernel, lds_max)) return rc;
+  hipLaunchKernelGGL(kernel, grid, block, lds, st, args);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? 0 : ffc_fail(std::string(what) + " launch: " + hipGetErrorString(e));
+}
+
+// FN<Geo, DT>::run(args...) of the plan's fft size and dtype (ffc::with_geo holds the table)
 template <template <class, int> class FN, class... A>
 static int ffc_dispatch(int N, int dtype, A&&... args) {
-  using namespace ffc;
-#define FFC_CASE(NN, a, b, c) \
-  case NN:                    \
-    return dtype == DT_BF16 ? FN<Geo<a, b, c>, DT_BF16>::run(args...) : FN<Geo<a, b, c>, DT_F16>::run(args...);
-  switch (N) {
-    FFC_CASE(256, 1, 16, 16)
-    FFC_CASE(512, 1, 16, 32)
-    FFC_CASE(1024, 1, 32, 32)
-    FFC_CASE(2048, 1, 32, 32)          // 2 passes of the 1024 kernel (inner-only multi-pass form, Body::InnerPass)
-    FFC_CASE(4096, 16, 16, 16)
-    FFC_CASE(8192, 32, 16, 16)
-    FFC_CASE(16384, 16, 32, 32)
-    FFC_CASE(32768, 32, 32, 32)
-    FFC_CASE(65536, 32, 32, 32)        // multi-pass sizes: R passes of the 32768 kernel (HostPlan::R, struct Pass)
-    FFC_CASE(131072, 32, 32, 32)
-  }
-#undef FFC_CASE
-  return ffc_fail("unsupported fft size");
+  int rc = 0;
+  const bool found = ffc::with_geo(N, [&](auto geo) {
+    using GEO = decltype(geo);
+    rc = dtype == ffc::DT_BF16 ? FN<GEO, ffc::DT_BF16>::run(args...) : FN<GEO, ffc::DT_F16>::run(args...);
+  });
+  return found ? rc : ffc_fail("unsupported fft size");
 }
 
 // pairs per chunk / number of chunks so the grid fills the chip (>= ~2 waves of workgroups) while a
 // workgroup still loops over several pairs of one head (k_f[h] reuse through L2).
-// fp32 dk_f partial-sum slabs per chunk: every geometry reduces its units inside the workgroup (Modes::w_acc_finish,
-// Modes::reduce_store_w) and writes one slab.
-static inline int ffc_slabs_per_chunk(const ffc_plan* p) { (void)p; return 1; }
-
-static inline void* ffc_zscratch(const ffc_plan* p, void* ws, int H, int nchunk);
 static inline void ffc_choose_chunks(const ffc_plan* p, int H, int npair, int* nchunk, int* ppc, bool fwd_only = false) {
   const bool outer = p->hp.N1 > 1;
   int upw = 8 / p->hp.NW;                       // units a workgroup processes per iteration
@@ -397,7 +392,7 @@ static inline void ffc_choose_chunks(const ffc_plan* p, int H, int npair, int* n
   *nchunk = (npair + *ppc - 1) / *ppc;
 }
 
-// spectrum scratch of the backward kernels: behind the fp32 dk_f slabs of the workspace (ffc_dkf_workspace_bytes)
+// spectrum scratch of the backward kernels: behind the fp32 dk_f slabs of the workspace (ffc_dkf_workspace_bytes), one slab per chunk
 static inline void* ffc_zscratch(const ffc_plan* p, void* ws, int H, int nchunk) {
-  return (uint8_t*)ws + (int64_t)nchunk * ffc_slabs_per_chunk(p) * H * p->hp.R * p->hp.NT * 2048 * 4;
+  return (uint8_t*)ws + (int64_t)nchunk * H * p->hp.R * p->hp.NT * 2048 * 4;
 }

@@ -27,11 +27,6 @@ __global__ __launch_bounds__(256) void mul_rows_kernel(const uint16_t* __restric
 
 // Fused backward: du = pregate * corr(dout*postgate, k), dpre = u * corr(...) (nullable, gated only) and the
 // dk_f partial sums in `ws` (same layout as ffc_conv_bwd_dkf; finish with ffc_kernel_ifft_grad).
-extern "C" int ffc_conv_fwd(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate, void* y,
-                            int64_t B, int64_t H, int64_t L, int conj_kf, void* stream);
-extern "C" int ffc_conv_bwd_gated(const ffc_plan* p, const void* dout, const void* u, const void* kf, const void* pregate,
-                                  const void* postgate, void* du, void* dpre, void* dpost, void* ws, int64_t B, int64_t H,
-                                  int64_t L, void* stream);
 extern "C" int ffc_conv_bwd(const ffc_plan* p, const void* dout, const void* u, const void* kf, const void* pregate,
                             const void* postgate, void* du, void* dpre, void* ws, int64_t B, int64_t H, int64_t L, void* stream) {
   return ffc_conv_bwd_gated(p, dout, u, kf, pregate, postgate, du, dpre, nullptr, ws, B, H, L, stream);
@@ -39,15 +34,35 @@ extern "C" int ffc_conv_bwd(const ffc_plan* p, const void* dout, const void* u, 
 // + dpost = dout * conv(u*pregate, k) (nullable).  Fused sizes >= 4096 produce it inside the same launch (one extra
 // inverse transform per pair); the single-tile sizes (fft <= 2048: the 1024 kernel and its 2-pass form) run the forward kernel with dout as the output gate.
 // Batch strides in elements (0 = contiguous H * L): every tensor may be a channel slice of a wider (B, C, L) tensor.
-extern "C" int ffc_conv_fwd_strided(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate,
-                                    void* y, int64_t B, int64_t H, int64_t L, int conj_kf, int64_t sb_u, int64_t sb_pre,
-                                    int64_t sb_post, int64_t sb_y, void* stream);
-extern "C" int64_t ffc_spectrum_bytes(const ffc_plan* p, int64_t B, int64_t H);
-static int conv_bwd_impl(const ffc_plan* p, const void* dout, const void* u, const void* kf, const void* pregate,
-                         const void* postgate, void* du, void* dpre, void* dpost, void* ws, const void* zin, int64_t B, int64_t H,
-                         int64_t L, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post,
-                         int64_t sb_du, int64_t sb_dpre, int64_t sb_dpost, void* stream, const void* yraw = nullptr,
-                         float* dk = nullptr, int64_t Lk = 0, bool* dk_done = nullptr, void* dk_pair = nullptr, float dk_pair_scale = 1.0f) {
+// One backward call, as the entry points below fill it (everything they do not name is zero / null).
+struct BwdCall {
+  const void *dout, *u, *kf, *pregate, *postgate;
+  void *du, *dpre, *dpost, *ws;
+  int64_t B, H, L;
+  void* stream;
+  int64_t sb_dout, sb_u, sb_pre, sb_post, sb_du, sb_dpre, sb_dpost;      // batch strides in elements, 0 = contiguous (H * L)
+  const void *zin, *yraw;              // what the forward saved: spectra, output before the postgate
+  // dk wanted from the same launch: real dk (H, Lk) fp32, or complex rows dk_pair with the caller's scale.  *dk_done says whether the
+  // launch wrote it; otherwise the slabs in ws hold dk_f and the caller finishes with ffc_kernel_ifft_grad(_c)
+  float* dk; int64_t Lk;
+  void* dk_pair; float dk_pair_scale;
+  bool* dk_done;
+};
+static BwdCall bwd_call(const void* dout, const void* u, const void* kf, const void* pregate, const void* postgate, void* du, void* dpre,
+                        void* dpost, void* ws, int64_t B, int64_t H, int64_t L, void* stream) {
+  BwdCall c{};
+  c.dout = dout; c.u = u; c.kf = kf; c.pregate = pregate; c.postgate = postgate; c.du = du; c.dpre = dpre; c.dpost = dpost; c.ws = ws;
+  c.B = B; c.H = H; c.L = L; c.stream = stream;
+  return c;
+}
+static void bwd_strides(BwdCall* c, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post, int64_t sb_du, int64_t sb_dpre, int64_t sb_dpost) {
+  c->sb_dout = sb_dout; c->sb_u = sb_u; c->sb_pre = sb_pre; c->sb_post = sb_post; c->sb_du = sb_du; c->sb_dpre = sb_dpre; c->sb_dpost = sb_dpost;
+}
+static int conv_bwd_impl(const ffc_plan* p, const BwdCall& c) {
+  const void *dout = c.dout, *u = c.u, *kf = c.kf, *pregate = c.pregate, *postgate = c.postgate, *zin = c.zin, *yraw = c.yraw;
+  void *du = c.du, *dpre = c.dpre, *dpost = c.dpost, *ws = c.ws, *stream = c.stream;
+  const int64_t B = c.B, H = c.H, L = c.L, Lk = c.Lk;
+  int64_t sb_dout = c.sb_dout, sb_u = c.sb_u, sb_pre = c.sb_pre, sb_post = c.sb_post, sb_du = c.sb_du, sb_dpre = c.sb_dpre, sb_dpost = c.sb_dpost;
   if (!p || !dout || !kf || !du || !ws) return ffc_fail("null arg");
   // `u` is read by the recomputing kernels, as the gate of dpregate and by the forward run that makes dpostgate without y_raw; on saved
   // spectra without gates nothing reads it and a null pointer says so (the HBM-level sizes' inner call, flashfftconv/conv.py _big_backward)
@@ -81,31 +96,16 @@ static int conv_bwd_impl(const ffc_plan* p, const void* dout, const void* u, con
   a.stream = p->env_stream >= 0 ? p->env_stream : ((!pregate && !postgate && p->hp.R == 1) ? 1 : 0);    // see Body::gload8
   a.flags = p->env_flags;                        // tuning flags: 2 = k_f streamed, 4 = scratch streamed
   d.dout = dout; d.ws = (float*)ws; d.du = du; d.dpre = dpre; d.zscratch = ffc_zscratch(p, ws, a.H, a.nchunk);
-  // dk from the same launch (Modes::dk_tail / dk_tail_multi): the workgroup owns all pairs of its head, fft 16384 / 32768 (8192 on request)
-  // (tuning flag 32 keeps the slab + ffc_kernel_ifft_grad pair)
-  // (fft 8192: the tail runs on 2 of the workgroup's 8 waves and measured +-0 / +2 % on the backward call, profiles/
-  // r04_ab_launch_fusion.txt: kept on the separate kernel unless tuning flag 128 asks for it)
-  if (dk && dk_done && a.nchunk == 1 && p->hp.N >= ((p->env_flags & 128) ? 8192 : 16384) && p->hp.N <= 32768 && p->hp.R == 1 &&
-      !(p->env_flags & 32) && Lk > 0 && Lk <= p->hp.N) {
-    d.dk_out = dk; d.Lk = (int)Lk; d.dk_scale = (float)(1.0 / p->hp.s_fwd);
-    d.tab_bf = p->d_blob_bf; d.t_bf = p->hp_bf.tabs;      // (fp16 plans: bf16 tables for the tail)
-    d.dk_fast = (Lk % 4 == 0) && !((uintptr_t)dk & 15);
-    *dk_done = true;
-  }
-  // multi-pass sizes (fft 65536 / 131072, bf16 plans): every pass ends with its share of dk (Modes::dk_tail_rp); tuning flag 32 as above
-  if (dk && dk_done && !*dk_done && a.nchunk == 1 && p->hp.R > 1 && p->hp.N1 > 1 && p->hp.dtype == DT_BF16 && !(p->env_flags & 32) &&
-      Lk > 0 && Lk <= p->hp.N) {
-    d.dk_out = dk; d.Lk = (int)Lk; d.dk_scale = (float)(1.0 / p->hp.s_fwd);
-    d.tab_bf = p->d_blob_bf; d.t_bf = p->hp_bf.tabs;
-    d.dk_fast = (Lk % 4 == 0) && !((uintptr_t)dk & 15);
-    *dk_done = true;
+  // dk from the same launch where the workgroup owns all pairs of its head (ffc::bwd_dk_form: Modes::dk_tail, or Modes::dk_tail_rp in every
+  // pass of the multi-pass sizes), on the plan's bf16 tables (fp16 plans too)
+  if (c.dk && c.dk_done && Lk > 0 && Lk <= p->hp.N && bwd_dk_form(p->hp, a.nchunk, p->env_flags, false) != DK_SEPARATE) {
+    set_dk_tail(&d, c.dk, nullptr, (int)Lk, (float)(1.0 / p->hp.s_fwd), (Lk % 4 == 0) && !((uintptr_t)c.dk & 15), p->d_blob_bf, p->hp_bf.tabs);
+    *c.dk_done = true;
   }
   // ... as complex rows (ffc_conv_bwd_kx: first step of dk at the HBM-level sizes; always bf16, the caller's scale)
-  if (dk_pair && dk_done && a.nchunk == 1 && p->hp.N >= ((p->env_flags & 128) ? 8192 : 16384) && p->hp.N <= 32768 && p->hp.R == 1 &&
-      !(p->env_flags & 32) && !((uintptr_t)dk_pair & 15)) {
-    d.dk_pair = dk_pair; d.Lk = p->hp.N; d.dk_scale = dk_pair_scale; d.dk_fast = 1;
-    d.tab_bf = p->d_blob_bf; d.t_bf = p->hp_bf.tabs;
-    *dk_done = true;
+  if (c.dk_pair && c.dk_done && !((uintptr_t)c.dk_pair & 15) && bwd_dk_form(p->hp, a.nchunk, p->env_flags, true) != DK_SEPARATE) {
+    set_dk_tail(&d, nullptr, c.dk_pair, p->hp.N, c.dk_pair_scale, 1, p->d_blob_bf, p->hp_bf.tabs);
+    *c.dk_done = true;
   }
   d.dpost = (p->hp.N1 > 1 || yraw) ? dpost : nullptr;      // with y_raw every geometry writes dpost from its dout row load
   d.zin = zin;
@@ -137,8 +137,9 @@ extern "C" int ffc_conv_bwd_gated_strided(const ffc_plan* p, const void* dout, c
                                           const void* postgate, void* du, void* dpre, void* dpost, void* ws, int64_t B, int64_t H,
                                           int64_t L, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post,
                                           int64_t sb_du, int64_t sb_dpre, int64_t sb_dpost, void* stream) {
-  return conv_bwd_impl(p, dout, u, kf, pregate, postgate, du, dpre, dpost, ws, nullptr, B, H, L, sb_dout, sb_u, sb_pre, sb_post, sb_du,
-                       sb_dpre, sb_dpost, stream);
+  BwdCall c = bwd_call(dout, u, kf, pregate, postgate, du, dpre, dpost, ws, B, H, L, stream);
+  bwd_strides(&c, sb_dout, sb_u, sb_pre, sb_post, sb_du, sb_dpre, sb_dpost);
+  return conv_bwd_impl(p, c);
 }
 // fused backward on the spectra saved by ffc_conv_fwd_z (same B, H, L, u, pregate): the first transform of every pair is skipped
 extern "C" int ffc_conv_bwd_z(const ffc_plan* p, const void* dout, const void* u, const void* kf, const void* pregate,
@@ -146,8 +147,10 @@ extern "C" int ffc_conv_bwd_z(const ffc_plan* p, const void* dout, const void* u
                               int64_t L, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post,
                               int64_t sb_du, int64_t sb_dpre, int64_t sb_dpost, void* stream) {
   if (!zin) return ffc_fail("null spectrum buffer");
-  return conv_bwd_impl(p, dout, u, kf, pregate, postgate, du, dpre, dpost, ws, zin, B, H, L, sb_dout, sb_u, sb_pre, sb_post, sb_du,
-                       sb_dpre, sb_dpost, stream);
+  BwdCall c = bwd_call(dout, u, kf, pregate, postgate, du, dpre, dpost, ws, B, H, L, stream);
+  bwd_strides(&c, sb_dout, sb_u, sb_pre, sb_post, sb_du, sb_dpre, sb_dpost);
+  c.zin = zin;
+  return conv_bwd_impl(p, c);
 }
 // ... and on the forward output before the postgate multiply that ffc_conv_fwd_z stored (y_raw, contiguous (B,H,L)): dpost =
 // dout * y_raw is written from the registers that hold the dout rows (same fp32 product, rounded once, as the output gate)
@@ -156,8 +159,10 @@ extern "C" int ffc_conv_bwd_zy(const ffc_plan* p, const void* dout, const void* 
                                int64_t B, int64_t H, int64_t L, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post,
                                int64_t sb_du, int64_t sb_dpre, int64_t sb_dpost, void* stream) {
   if ((!zin && !(p && p->hp.N1 <= 1)) || !y_raw || !dpost) return ffc_fail("null spectrum / y_raw / dpost buffer (y_raw alone: single-tile sizes, fft <= 2048)");
-  return conv_bwd_impl(p, dout, u, kf, pregate, postgate, du, dpre, dpost, ws, zin, B, H, L, sb_dout, sb_u, sb_pre, sb_post, sb_du,
-                       sb_dpre, sb_dpost, stream, y_raw);
+  BwdCall c = bwd_call(dout, u, kf, pregate, postgate, du, dpre, dpost, ws, B, H, L, stream);
+  bwd_strides(&c, sb_dout, sb_u, sb_pre, sb_post, sb_du, sb_dpre, sb_dpost);
+  c.zin = zin; c.yraw = y_raw;
+  return conv_bwd_impl(p, c);
 }
 extern "C" int ffc_conv_bwd_gated(const ffc_plan* p, const void* dout, const void* u, const void* kf, const void* pregate,
                                   const void* postgate, void* du, void* dpre, void* dpost, void* ws, int64_t B, int64_t H,
@@ -168,15 +173,15 @@ extern "C" int ffc_conv_bwd_gated(const ffc_plan* p, const void* dout, const voi
 // The module's whole backward in one call: du (+ dpre, dpost) and dk (H, Lk) fp32; zin / y_raw: what ffc_conv_fwd_k saved (nullable:
 // recomputing kernel).  dk comes out of the backward launch itself where a workgroup owns its head (Modes::dk_tail), through the
 // fp32 slabs in ws + ffc_kernel_ifft_grad otherwise.
-extern "C" int ffc_kernel_ifft_grad(const ffc_plan* p, const void* ws, int64_t B, int64_t H, int64_t Lk, float* dk, void* stream);
 extern "C" int ffc_conv_bwd_k(const ffc_plan* p, const void* dout, const void* u, const void* kf, const void* pregate, const void* postgate,
                               void* du, void* dpre, void* dpost, void* ws, const void* zin, const void* y_raw, float* dk, int64_t Lk,
                               int64_t B, int64_t H, int64_t L, void* stream) {
   if (!dk) return ffc_fail("null dk");
   bool dk_done = false;
-  const void* yr = ((zin || p->hp.N1 <= 1) && y_raw && dpost) ? y_raw : nullptr;
-  int rc = conv_bwd_impl(p, dout, u, kf, pregate, postgate, du, dpre, dpost, ws, zin, B, H, L, 0, 0, 0, 0, 0, 0, 0, stream, yr, dk, Lk,
-                         &dk_done);
+  BwdCall c = bwd_call(dout, u, kf, pregate, postgate, du, dpre, dpost, ws, B, H, L, stream);
+  c.zin = zin; c.yraw = ((zin || p->hp.N1 <= 1) && y_raw && dpost) ? y_raw : nullptr;
+  c.dk = dk; c.Lk = Lk; c.dk_done = &dk_done;
+  int rc = conv_bwd_impl(p, c);
   if (rc || dk_done) return rc;
   return ffc_kernel_ifft_grad(p, ws, B, H, Lk, dk, stream);
 }
@@ -184,13 +189,13 @@ extern "C" int ffc_conv_bwd_k(const ffc_plan* p, const void* dout, const void* u
 // The backward of an HBM-level size's inner convolution in one call: input-gradient rows du and the dk rows as a complex pair-plane
 // tensor (2, H, N) bf16 (as ffc_kernel_ifft_grad_c with `scale`), out of the backward launch itself where a workgroup owns its
 // "head", through the fp32 slabs in ws otherwise.  zin: the spectra ffc_conv_fwd_kx kept (nullable).
-extern "C" int ffc_kernel_ifft_grad_c(const ffc_plan* p, const void* ws, int64_t B, int64_t H, void* outpair, float scale, void* stream);
 extern "C" int ffc_conv_bwd_kx(const ffc_plan* p, const void* dout, const void* u, const void* kf, void* du, void* ws, const void* zin,
                                void* outpair, float scale, int64_t B, int64_t H, int64_t L, void* stream) {
   if (!outpair) return ffc_fail("null outpair");
   bool dk_done = false;
-  int rc = conv_bwd_impl(p, dout, u, kf, nullptr, nullptr, du, nullptr, nullptr, ws, zin, B, H, L, 0, 0, 0, 0, 0, 0, 0, stream, nullptr,
-                         nullptr, 0, &dk_done, outpair, scale);
+  BwdCall c = bwd_call(dout, u, kf, nullptr, nullptr, du, nullptr, nullptr, ws, B, H, L, stream);
+  c.zin = zin; c.dk_pair = outpair; c.dk_pair_scale = scale; c.dk_done = &dk_done;
+  int rc = conv_bwd_impl(p, c);
   if (rc || dk_done) return rc;
   return ffc_kernel_ifft_grad_c(p, ws, B, H, outpair, scale, stream);
 }

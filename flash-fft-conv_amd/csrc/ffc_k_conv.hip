@@ -1,8 +1,8 @@
 // FlashFFTConv forward / input-gradient kernel (see ffc_body.h) + ffc_conv_fwd.
-#include "ffc_dev.h"
+#include "ffc_conv_launch.h"
 using namespace ffc;
 
-static constexpr int SMALL_WAVES = 2;      // waves per SIMD the single-tile kernels (no outer digit) are compiled for
+static constexpr int SMALL_WAVES = 2;     // waves per SIMD the single-tile kernels (no outer digit) are compiled for
 // SZ: the forward that also stores the pairs' spectra for the backward pass (ConvArgs::zsave; fused sizes with an outer digit)
 template <class GEO, int DT, bool HALF, bool SZ = false, bool SP = false>
 __global__ __launch_bounds__(GEO::WGW * 64, GEO::OUTER ? 2 : SMALL_WAVES) void conv_kernel(ConvArgs a) {
@@ -64,110 +64,28 @@ __global__ __launch_bounds__(GEO::WGW * 64, 2) void conv_rp_kernel(ConvArgs a) {
   }
 }
 
-template <class GEO, int DT>
-struct ConvLaunch {
-  static int run(const ConvArgs& a, hipStream_t st) {
-    using BD = Body<DevB, GEO, DT>;
-    int hpad = (a.H + 7) & ~7;
-    int grid = hpad * a.nchunk;
-    if (a.R > 1) {
-      if constexpr (GEO::N == 32768) {
-        if (a.zsave) {
-          if (16 * GEO::Mi >= a.L) {
-            int rc = ffc_set_lds(conv_rp_kernel<GEO, DT, true, true>, GEO::LDS_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL((conv_rp_kernel<GEO, DT, true, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-          } else {
-            int rc = ffc_set_lds(conv_rp_kernel<GEO, DT, false, true>, GEO::LDS_BYTES);
-            if (rc) return rc;
-            hipLaunchKernelGGL((conv_rp_kernel<GEO, DT, false, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-          }
-          hipError_t e = hipGetLastError();
-          return e == hipSuccess ? 0 : ffc_fail(std::string("conv_rp_kernel (spectrum-saving) launch: ") + hipGetErrorString(e));
-        }
-        if (16 * GEO::Mi >= a.L) {
-          int rc = ffc_set_lds(conv_rp_kernel<GEO, DT, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_rp_kernel<GEO, DT, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        } else {
-          int rc = ffc_set_lds(conv_rp_kernel<GEO, DT, false>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_rp_kernel<GEO, DT, false>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("conv_rp_kernel launch: ") + hipGetErrorString(e));
-      } else if constexpr (GEO::N == 1024) {
-        constexpr int lds = GEO::LDS_BYTES + 2 * BD::IPASS_BYTES;
-        const int cap = (a.persist > 0 && a.persist < (1 << 29)) ? 2 * a.persist : (1 << 30);      // FFC_PERSIST=0: uncapped
-        if (a.zsave || a.yraw) {
-          int rc = ffc_set_lds(conv_rp_kernel<GEO, DT, false, true>, lds);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_rp_kernel<GEO, DT, false, true>), dim3(grid > cap ? cap : grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES + a.R * BD::IPASS_BYTES, st, a);
-        } else {
-          int rc = ffc_set_lds(conv_rp_kernel<GEO, DT, false>, lds);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_rp_kernel<GEO, DT, false>), dim3(grid > cap ? cap : grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES + a.R * BD::IPASS_BYTES, st, a);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("conv_rp_kernel launch: ") + hipGetErrorString(e));
-      } else {
-        return ffc_fail("multi-pass plan on a geometry without multi-pass kernels");
-      }
-    }
-    if (GEO::OUTER && GEO::NW == 1 && grid > a.persist) grid = a.persist;      // persistent: one workgroup per CU
-    if (!GEO::OUTER && a.persist > 0 && a.persist < (1 << 29) && grid > 2 * a.persist) grid = 2 * a.persist;      // persistent: two per CU
-    if (a.sparse) {
-      if constexpr (GEO::HAS_SP) {
-        if ((GEO::N1 / 2) * GEO::Mi >= a.L) {
-          int rc = ffc_set_lds(conv_kernel<GEO, DT, true, false, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_kernel<GEO, DT, true, false, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        } else {
-          int rc = ffc_set_lds(conv_kernel<GEO, DT, false, false, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_kernel<GEO, DT, false, false, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("conv_kernel (frequency-sparse) launch: ") + hipGetErrorString(e));
-      } else {
-        return ffc_fail("frequency-sparse kernel: fft 16384 / 32768 only");
-      }
-    }
-    if (a.zsave || (!GEO::OUTER && a.yraw)) {
-      if constexpr (GEO::OUTER) {
-        if ((GEO::N1 / 2) * GEO::Mi >= a.L) {
-          int rc = ffc_set_lds(conv_kernel<GEO, DT, true, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_kernel<GEO, DT, true, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        } else {
-          int rc = ffc_set_lds(conv_kernel<GEO, DT, false, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((conv_kernel<GEO, DT, false, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("conv_kernel (spectrum-saving) launch: ") + hipGetErrorString(e));
-      } else {
-        int rc = ffc_set_lds(conv_kernel<GEO, DT, false, true>, GEO::LDS_BYTES);
-        if (rc) return rc;
-        hipLaunchKernelGGL((conv_kernel<GEO, DT, false, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("conv_kernel (spectrum-saving, single tile) launch: ") + hipGetErrorString(e));
-      }
-    }
-    // HALF variant (own register allocation): 32-point outer digit and L <= N/2, only E rows < 16 carry data
-    if (GEO::OUTER && (GEO::N1 / 2) * GEO::Mi >= a.L) {
-      int rc = ffc_set_lds(conv_kernel<GEO, DT, true>, GEO::LDS_BYTES);
-      if (rc) return rc;
-      hipLaunchKernelGGL((conv_kernel<GEO, DT, true>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-    } else {
-      int rc = ffc_set_lds(conv_kernel<GEO, DT, false>, GEO::LDS_BYTES);
-      if (rc) return rc;
-      hipLaunchKernelGGL((conv_kernel<GEO, DT, false>), dim3(grid), dim3(GEO::WGW * 64), GEO::LDS_BYTES, st, a);
-    }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : ffc_fail(std::string("conv_kernel launch: ") + hipGetErrorString(e));
+// this unit's kernels for the shared launcher (ffc_conv_launch.h)
+struct ConvKernels {
+  static constexpr bool HAS_ADD = false;
+  template <class GEO, int DT, bool MP, bool HALF, bool SZ, bool SP>
+  static constexpr auto kernel() {
+    if constexpr (MP) return conv_rp_kernel<GEO, DT, HALF, SZ>;
+    else return conv_kernel<GEO, DT, HALF, SZ, SP>;
+  }
+  static const char* what(bool mp, bool sz, bool sp, bool outer) {
+    if (mp) return sz && outer ? "conv_rp_kernel (spectrum-saving)" : "conv_rp_kernel";
+    if (sz) return outer ? "conv_kernel (spectrum-saving)" : "conv_kernel (spectrum-saving, single tile)";
+    return sp ? "conv_kernel (frequency-sparse)" : "conv_kernel";
   }
 };
+// The HALF form of the single-tile sizes is never launched (there is no outer digit to halve).  The launcher once instantiated it by
+// accident; the instantiations stay so that the library's kernel set is what it was.
+template __global__ void conv_kernel<Geo<1, 16, 16>, DT_BF16, true>(ConvArgs);
+template __global__ void conv_kernel<Geo<1, 16, 16>, DT_F16, true>(ConvArgs);
+template __global__ void conv_kernel<Geo<1, 16, 32>, DT_BF16, true>(ConvArgs);
+template __global__ void conv_kernel<Geo<1, 16, 32>, DT_F16, true>(ConvArgs);
+template __global__ void conv_kernel<Geo<1, 32, 32>, DT_BF16, true>(ConvArgs);
+template __global__ void conv_kernel<Geo<1, 32, 32>, DT_F16, true>(ConvArgs);
 
 // stride 0 = contiguous (H * L)
 static inline bool ffc_stride_ok(int64_t* sb, int64_t B, int64_t H, int64_t L) {
@@ -184,11 +102,42 @@ extern "C" int64_t ffc_spectrum_bytes(const ffc_plan* p, int64_t B, int64_t H) {
   }
   return ((B + 1) / 2) * H * (int64_t)p->hp.N * 4;        // (hp.N = the plan's fft size, R passes x the kernel size)
 }
-static int conv_fwd_impl(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate,
-                         void* y, void* zsave, void* yraw, int sparse, int64_t B, int64_t H, int64_t L, int conj_kf, int64_t sb_u, int64_t sb_pre,
-                         int64_t sb_post, int64_t sb_y, void* stream, const float* kfuse_k = nullptr, int64_t kfuse_Lk = 0,
-                         bool* kfuse_done = nullptr, const void* kfuse_x = nullptr, float kfuse_xscale = 1.0f, const void* addend = nullptr,
-                         int64_t sb_add = 0) {
+
+// One forward call, as the entry points below fill it (everything they do not name is zero / null).
+struct FwdCall {
+  const void *u, *kf, *pregate, *postgate;
+  void* y;
+  int64_t B, H, L;
+  void* stream;
+  int conj_kf;
+  int64_t sb_u, sb_pre, sb_post, sb_y;      // batch strides in elements, 0 = contiguous (H * L)
+  void *zsave, *yraw;                       // spectra / output before the postgate, for the backward pass
+  int sparse;                               // > 0: frequency-sparse k_f (ffc_conv_fwd_sparse)
+  const void* addend; int64_t sb_add;       // ffc_conv_fwd_res
+  // k -> k_f inside the launch, from real k (H, kfuse_Lk) fp32 or from complex rows kfuse_x with the caller's scale: given only when
+  // kfft_in_launch() said so
+  const float* kfuse_k; int64_t kfuse_Lk;
+  const void* kfuse_x; float kfuse_xscale;
+};
+static FwdCall fwd_call(const void* u, const void* kf, const void* pregate, const void* postgate, void* y, int64_t B, int64_t H, int64_t L,
+                        void* stream) {
+  FwdCall c{};
+  c.u = u; c.kf = kf; c.pregate = pregate; c.postgate = postgate; c.y = y; c.B = B; c.H = H; c.L = L; c.stream = stream;
+  return c;
+}
+// whether the convolution launch of (B, H) takes the k -> k_f step (ffc::fwd_takes_kfft on the chunking the launch will use)
+static bool kfft_in_launch(const ffc_plan* p, int64_t B, int64_t H) {
+  int nchunk = 0, ppc = 0;
+  if (B > 0 && H > 0) ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc, true);
+  return fwd_takes_kfft(p->hp, nchunk, 0, p->env_flags);
+}
+
+static int conv_fwd_impl(const ffc_plan* p, const FwdCall& c) {
+  const void *u = c.u, *kf = c.kf, *pregate = c.pregate, *postgate = c.postgate, *addend = c.addend;
+  void *y = c.y, *zsave = c.zsave;
+  const int64_t B = c.B, H = c.H, L = c.L;
+  const int sparse = c.sparse;
+  int64_t sb_u = c.sb_u, sb_pre = c.sb_pre, sb_post = c.sb_post, sb_y = c.sb_y, sb_add = c.sb_add;
   if (!p || !u || !kf || !y) return ffc_fail("null arg");
   if (B <= 0 || H <= 0) return ffc_fail("empty batch/heads");
   if (L <= 0 || L > p->hp.N) return ffc_fail("L must be in (0, fft_size]");
@@ -202,10 +151,10 @@ static int conv_fwd_impl(const ffc_plan* p, const void* u, const void* kf, const
   a.B = (int)B; a.H = (int)H; a.L = (int)L; a.npair = (int)((B + 1) / 2);
   a.sbu = sb_u; a.sbg = sb_pre; a.sbp = sb_post; a.sby = sb_y;
   a.addend = addend; a.sba = sb_add;
-  a.conj_kf = conj_kf;
+  a.conj_kf = c.conj_kf;
   // y_raw without the spectra: the single-tile sizes (fft <= 2048) only -- their backward transforms u * pregate again from rows it
   // loads anyway (dpregate, du) and takes dpostgate = dout * y_raw from its dout row load (round 6)
-  a.zsave = zsave; a.yraw = (zsave || p->hp.N1 <= 1) ? yraw : nullptr;
+  a.zsave = zsave; a.yraw = (zsave || p->hp.N1 <= 1) ? c.yraw : nullptr;
   a.sparse = sparse;
   if (sparse && (sparse < 0 || sparse > 4 || zsave || p->hp.R > 1 || p->hp.N2 != 32 || p->hp.N3 != 32 || p->hp.N1 <= 1))
     return ffc_fail("frequency-sparse forward: fft 16384 / 32768, 1 <= rows <= 4, no spectrum buffer");
@@ -217,31 +166,26 @@ static int conv_fwd_impl(const ffc_plan* p, const void* u, const void* kf, const
   ffc_choose_chunks(p, a.H, a.npair, &a.nchunk, &a.ppc, true);
   a.persist = ffc_persist(p);
   a.R = p->hp.R;
-  // k -> k_f inside this launch (Modes::kfft_head): a workgroup owns its head, fft 8192 / 16384 / 32768 (the sizes whose waves
-  // meet at workgroup barriers anyway); tuning flag 64 keeps the separate launch
-  if (kfuse_k && kfuse_done && a.nchunk == 1 && p->hp.N >= 8192 && p->hp.N <= 32768 && p->hp.R == 1 && !sparse &&
-      !(p->env_flags & 64) && kfuse_Lk > 0 && kfuse_Lk <= p->hp.N && H * kfuse_Lk < ((int64_t)1 << 31)) {
-    a.kfuse_k = kfuse_k; a.kfuse_Lk = (int)kfuse_Lk;
+  // k -> k_f inside this launch (Modes::kfft_head), where the caller found that it may be (kfft_in_launch)
+  if (c.kfuse_k) {
+    a.kfuse_k = c.kfuse_k; a.kfuse_Lk = (int)c.kfuse_Lk;
     a.kfuse_scale = (float)(p->hp.s_k / p->hp.s_fwd) / (p->hp.dtype == DT_F16 ? 256.f : 1.f);
-    a.kfuse_fast = (kfuse_Lk % 4 == 0) && !((uintptr_t)kfuse_k & 15);
-    *kfuse_done = true;
+    a.kfuse_fast = (c.kfuse_Lk % 4 == 0) && !((uintptr_t)c.kfuse_k & 15);
   }
   // ... from complex rows (ffc_conv_fwd_kx: the inner k_f rows of the HBM-level sizes, the caller's scale)
-  if (kfuse_x && kfuse_done && a.nchunk == 1 && p->hp.N >= 8192 && p->hp.N <= 32768 && p->hp.R == 1 && !sparse &&
-      !(p->env_flags & 64) && !((uintptr_t)kfuse_x & 15)) {
-    a.kfuse_x = kfuse_x; a.kfuse_scale = kfuse_xscale; a.kfuse_Lk = p->hp.N; a.kfuse_fast = 1;
-    *kfuse_done = true;
-  }
+  if (c.kfuse_x) { a.kfuse_x = c.kfuse_x; a.kfuse_scale = c.kfuse_xscale; a.kfuse_Lk = p->hp.N; a.kfuse_fast = 1; }
   // every row is read / written exactly once per launch (multi-pass sizes re-read the rows in every pass: plain accesses)
   a.stream = p->env_stream >= 0 ? p->env_stream : (p->hp.R > 1 ? 0 : 1);
-  if (addend) return ffc_conv_res_launch(p->hp.N, p->hp.dtype, a, (hipStream_t)stream);      // kernels of their own (ffc_k_conv_res.hip)
-  return ffc_dispatch<ConvLaunch>(p->hp.N, p->hp.dtype, a, (hipStream_t)stream);
+  if (addend) return ffc_conv_res_launch(p->hp.N, p->hp.dtype, a, (hipStream_t)c.stream);      // kernels of their own (ffc_k_conv_res.hip)
+  return ffc_dispatch<ConvLaunch<ConvKernels>::T>(p->hp.N, p->hp.dtype, a, (hipStream_t)c.stream);
 }
 
 extern "C" int ffc_conv_fwd_strided(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate,
                                     void* y, int64_t B, int64_t H, int64_t L, int conj_kf, int64_t sb_u, int64_t sb_pre,
                                     int64_t sb_post, int64_t sb_y, void* stream) {
-  return conv_fwd_impl(p, u, kf, pregate, postgate, y, nullptr, nullptr, 0, B, H, L, conj_kf, sb_u, sb_pre, sb_post, sb_y, stream);
+  FwdCall c = fwd_call(u, kf, pregate, postgate, y, B, H, L, stream);
+  c.conj_kf = conj_kf; c.sb_u = sb_u; c.sb_pre = sb_pre; c.sb_post = sb_post; c.sb_y = sb_y;
+  return conv_fwd_impl(p, c);
 }
 // forward that also stores every pair's spectrum FFT(u * pregate) in `zsave` (ffc_spectrum_bytes) for ffc_conv_bwd_z and,
 // when y_raw is given (16-byte aligned, contiguous (B,H,L)), the output before the postgate multiply
@@ -250,7 +194,9 @@ extern "C" int ffc_conv_fwd_z(const ffc_plan* p, const void* u, const void* kf, 
                               int64_t sb_y, void* stream) {
   if (!zsave && !(y_raw && p && p->hp.N1 <= 1)) return ffc_fail("null spectrum buffer (y_raw alone: single-tile sizes, fft <= 2048)");
   if (y_raw && ((uintptr_t)y_raw & 15)) return ffc_fail("y_raw must be 16-byte aligned");
-  return conv_fwd_impl(p, u, kf, pregate, postgate, y, zsave, y_raw, 0, B, H, L, 0, sb_u, sb_pre, sb_post, sb_y, stream);
+  FwdCall c = fwd_call(u, kf, pregate, postgate, y, B, H, L, stream);
+  c.zsave = zsave; c.yraw = y_raw; c.sb_u = sb_u; c.sb_pre = sb_pre; c.sb_post = sb_post; c.sb_y = sb_y;
+  return conv_fwd_impl(p, c);
 }
 
 // y = postgate * conv(u * pregate, k) + addend: the superset of ffc_conv_fwd_strided and ffc_conv_fwd_z (zsave / y_raw nullable, y_raw
@@ -269,8 +215,10 @@ extern "C" int ffc_conv_fwd_res(const ffc_plan* p, const void* u, const void* kf
     const uintptr_t y0 = (uintptr_t)y, y1 = y0 + (uintptr_t)(((B - 1) * sy + H * L) * 2);
     if (a0 < y1 && y0 < a1) return ffc_fail("addend overlaps y");
   }
-  return conv_fwd_impl(p, u, kf, pregate, postgate, y, zsave, y_raw, 0, B, H, L, conj_kf, sb_u, sb_pre, sb_post, sb_y, stream,
-                       nullptr, 0, nullptr, nullptr, 1.0f, addend, sb_add);
+  FwdCall c = fwd_call(u, kf, pregate, postgate, y, B, H, L, stream);
+  c.conj_kf = conj_kf; c.zsave = zsave; c.yraw = y_raw; c.addend = addend;
+  c.sb_u = sb_u; c.sb_pre = sb_pre; c.sb_post = sb_post; c.sb_y = sb_y; c.sb_add = sb_add;
+  return conv_fwd_impl(p, c);
 }
 
 // Forward / input-gradient pass with a LOW-PASS k_f: every non-zero bin f has k3 = f / (N1 N2) < rows or >= 32 - rows
@@ -280,7 +228,9 @@ extern "C" int ffc_conv_fwd_res(const ffc_plan* p, const void* u, const void* kf
 extern "C" int ffc_conv_fwd_sparse(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate,
                                    void* y, int64_t B, int64_t H, int64_t L, int conj_kf, int rows, void* stream) {
   if (rows < 1) return ffc_fail("frequency-sparse forward: rows must be >= 1");
-  return conv_fwd_impl(p, u, kf, pregate, postgate, y, nullptr, nullptr, rows, B, H, L, conj_kf, 0, 0, 0, 0, stream);
+  FwdCall c = fwd_call(u, kf, pregate, postgate, y, B, H, L, stream);
+  c.conj_kf = conj_kf; c.sparse = rows;
+  return conv_fwd_impl(p, c);
 }
 
 extern "C" int ffc_conv_fwd(const ffc_plan* p, const void* u, const void* kf, const void* pregate, const void* postgate, void* y,
@@ -320,58 +270,42 @@ extern "C" int ffc_conv_fwd_prof(const ffc_plan* p, const void* u, const void* k
   a.flags = p->env_flags;
   a.prof = prof;
   ffc_choose_chunks(p, a.H, a.npair, &a.nchunk, &a.ppc);
-  int rc = ffc_set_lds(conv_prof_kernel<GEO, DT_BF16>, GEO::LDS_BYTES);
-  if (rc) return rc;
-  int hpad = (a.H + 7) & ~7;
-  if (grid_out) *grid_out = hpad * a.nchunk;
-  hipLaunchKernelGGL((conv_prof_kernel<GEO, DT_BF16>), dim3(hpad * a.nchunk), dim3(512), GEO::LDS_BYTES, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? 0 : ffc_fail(hipGetErrorString(e));
+  const int grid = fwd_route<GEO>(a).grid;
+  if (grid_out) *grid_out = grid;
+  return ffc_launch(conv_prof_kernel<GEO, DT_BF16>, "conv_prof_kernel", grid, GEO::WGW * 64, GEO::LDS_BYTES, GEO::LDS_BYTES, (hipStream_t)stream, a);
 }
 
 // The module's forward in one call (see ffc_hip.hip for the backward's): k (H, Lk) fp32 -> kf_out, then y = postgate * conv(u *
 // pregate, k); zsave / y_raw as in ffc_conv_fwd_z (both nullable).  Where a workgroup owns its head the k -> k_f step runs inside
 // the convolution launch (Modes::kfft_head); otherwise ffc_kernel_fft first.
-extern "C" int ffc_kernel_fft(const ffc_plan* p, const float* k, int64_t H, int64_t Lk, void* kf, void* stream);
 extern "C" int ffc_conv_fwd_k(const ffc_plan* p, const float* k, int64_t Lk, void* kf_out, const void* u, const void* pregate,
                               const void* postgate, void* y, void* zsave, void* y_raw, int64_t B, int64_t H, int64_t L, void* stream) {
   if (!p || !k || !kf_out) return ffc_fail("null arg");
   if (y_raw && ((uintptr_t)y_raw & 15)) return ffc_fail("y_raw must be 16-byte aligned");
-  // decide first whether the convolution launch can take the k -> k_f step (same rule as conv_fwd_impl applies below)
-  int nchunk = 0, ppc = 0;
-  if (B > 0 && H > 0) ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc, true);
-  const bool fuse = nchunk == 1 && p->hp.N >= 8192 && p->hp.N <= 32768 && p->hp.R == 1 && !(p->env_flags & 64) && Lk > 0 &&
-                    Lk <= p->hp.N && H * Lk < ((int64_t)1 << 31);
+  const bool fuse = kfft_in_launch(p, B, H) && Lk > 0 && Lk <= p->hp.N && H * Lk < ((int64_t)1 << 31);
   if (!fuse) {
     int rc = ffc_kernel_fft(p, k, H, Lk, kf_out, stream);
     if (rc) return rc;
   }
-  bool done = false;
-  int rc = conv_fwd_impl(p, u, kf_out, pregate, postgate, y, zsave, y_raw, 0, B, H, L, 0, 0, 0, 0, 0, stream,
-                         fuse ? k : nullptr, Lk, &done);
-  if (rc) return rc;
-  if (fuse && !done) return ffc_fail("internal: the convolution launch did not take the k -> k_f step");
-  return 0;
+  FwdCall c = fwd_call(u, kf_out, pregate, postgate, y, B, H, L, stream);
+  c.zsave = zsave; c.yraw = y_raw;
+  if (fuse) { c.kfuse_k = k; c.kfuse_Lk = Lk; }
+  return conv_fwd_impl(p, c);
 }
 
 // The forward of an HBM-level size's inner convolution in one call: the inner k_f rows from their complex input (pair-plane tensor
 // (2, H, N), as ffc_kernel_fft_c; `scale` = that call's scale) into kf_out, then the convolution of the rows `u` (no gates at this
 // level), spectra kept in zsave when given.  k -> k_f runs inside the convolution launch where a workgroup owns its "head".
-extern "C" int ffc_kernel_fft_c(const ffc_plan* p, const void* xpair, int64_t H, void* kf, float scale, void* stream);
 extern "C" int ffc_conv_fwd_kx(const ffc_plan* p, const void* xpair, float scale, void* kf_out, const void* u, void* y, void* zsave,
                                int64_t B, int64_t H, int64_t L, void* stream) {
   if (!p || !xpair || !kf_out) return ffc_fail("null arg");
-  int nchunk = 0, ppc = 0;
-  if (B > 0 && H > 0) ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc, true);
-  const bool fuse = nchunk == 1 && p->hp.N >= 8192 && p->hp.N <= 32768 && p->hp.R == 1 && !(p->env_flags & 64) && !((uintptr_t)xpair & 15);
+  const bool fuse = kfft_in_launch(p, B, H) && !((uintptr_t)xpair & 15);
   if (!fuse) {
     int rc = ffc_kernel_fft_c(p, xpair, H, kf_out, scale, stream);
     if (rc) return rc;
   }
-  bool done = false;
-  int rc = conv_fwd_impl(p, u, kf_out, nullptr, nullptr, y, zsave, nullptr, 0, B, H, L, 0, 0, 0, 0, 0, stream, nullptr, 0, &done,
-                         fuse ? xpair : nullptr, scale);
-  if (rc) return rc;
-  if (fuse && !done) return ffc_fail("internal: the convolution launch did not take the k -> k_f step");
-  return 0;
+  FwdCall c = fwd_call(u, kf_out, nullptr, nullptr, y, B, H, L, stream);
+  c.zsave = zsave;
+  if (fuse) { c.kfuse_x = xpair; c.kfuse_xscale = scale; }
+  return conv_fwd_impl(p, c);
 }

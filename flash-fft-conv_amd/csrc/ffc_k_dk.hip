@@ -11,12 +11,9 @@ struct DkLaunch {
   static int run(const DkArgs& a, hipStream_t st) {
     using BD = Body<DevB, GEO, DT>;
     const int lds = GEO::LDS_BYTES + ((!GEO::OUTER && a.R > 1) ? a.R * BD::IPASS_BYTES : 0);   // inner-only multi-pass tables
-    int rc = ffc_set_lds(dkifft_kernel<GEO, DT>, GEO::LDS_BYTES + (GEO::OUTER ? 0 : 2 * BD::IPASS_BYTES));
-    if (rc) return rc;
     const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
-    hipLaunchKernelGGL((dkifft_kernel<GEO, DT>), dim3((nunits + GEO::UPW - 1) / GEO::UPW), dim3(GEO::WGW * 64), lds, st, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : ffc_fail(std::string("dkifft_kernel launch: ") + hipGetErrorString(e));
+    return ffc_launch(dkifft_kernel<GEO, DT>, "dkifft_kernel", (nunits + GEO::UPW - 1) / GEO::UPW, GEO::WGW * 64,
+                      GEO::LDS_BYTES + (GEO::OUTER ? 0 : 2 * BD::IPASS_BYTES), lds, st, a);
   }
 };
 
@@ -47,7 +44,7 @@ extern "C" int ffc_kernel_ifft_grad(const ffc_plan* p, const void* ws, int64_t B
   DkArgs a{};
   // always bf16 arithmetic: W/N underflows fp16 for small gradients, bf16 keeps fp32's range
   a.ws = (const float*)ws; a.dk = dk; a.tab = p->d_blob_bf; a.t = p->hp_bf.tabs; a.H = (int)H; a.Lk = (int)Lk;
-  a.nslab = nchunk * ffc_slabs_per_chunk(p);
+  a.nslab = nchunk;
   a.scale = (float)(1.0 / p->hp.s_fwd); a.s_inv = (float)p->hp_bf.s_inv;   // tile_inv applies s_inv = 1/(N s_fwd)
   a.fast = (Lk % 4 == 0) && !((uintptr_t)dk & 15);
   a.flags = p->env_flags;
@@ -63,7 +60,7 @@ extern "C" int ffc_kernel_ifft_grad_c(const ffc_plan* p, const void* ws, int64_t
   ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc);
   DkArgs a{};
   a.ws = (const float*)ws; a.outpair = outpair; a.tab = p->d_blob_bf; a.t = p->hp_bf.tabs; a.H = (int)H; a.Lk = p->hp.N;
-  a.nslab = nchunk * ffc_slabs_per_chunk(p); a.scale = scale; a.s_inv = (float)p->hp_bf.s_inv; a.fast = 1;
+  a.nslab = nchunk; a.scale = scale; a.s_inv = (float)p->hp_bf.s_inv; a.fast = 1;
   a.R = p->hp.R;
   return ffc_dispatch<DkLaunch>(p->hp.N, DT_BF16, a, (hipStream_t)stream);
 }

@@ -39,54 +39,24 @@ __global__ __launch_bounds__(GEO::WGW * 64, 2) __attribute__((amdgpu_num_vgpr(12
 #pragma unroll 1
   for (int k0 = 0; k0 < d.c.R; k0++) Modes<DevBO, GEO, DT>::template dkf<HALF, true>(d, h, chunk, wg, k0, wv);
 }
+// the variant, grid and LDS rules are ffc::bwd_route (ffc_route.h)
 template <class GEO, int DT>
 struct DkfLaunch {
   static int run(const DkfArgs& d, hipStream_t st) {
-    int hpad = (d.c.H + 7) & ~7;
-    int ngrid = hpad * d.c.nchunk;
-    if (d.c.R > 1) {
-      if constexpr (GEO::N == 32768) {
-        const dim3 grid(ngrid), block(GEO::WGW * 64);
-        if (16 * GEO::Mi >= d.c.L) {
-          int rc = ffc_set_lds(dkf_rp_kernel<GEO, DT, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((dkf_rp_kernel<GEO, DT, true>), grid, block, GEO::LDS_BYTES, st, d);
-        } else {
-          int rc = ffc_set_lds(dkf_rp_kernel<GEO, DT, false>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((dkf_rp_kernel<GEO, DT, false>), grid, block, GEO::LDS_BYTES, st, d);
-        }
-        hipError_t e = hipGetLastError();
-        return e == hipSuccess ? 0 : ffc_fail(std::string("dkf_rp_kernel launch: ") + hipGetErrorString(e));
-      } else if constexpr (GEO::OUTER) {
-        return ffc_fail("multi-pass plan on a geometry without multi-pass kernels");
-      }
-    }
-    if (GEO::OUTER && GEO::NW == 1 && d.c.persist > 0 && ngrid > d.c.persist) ngrid = d.c.persist;   // persistent: one per CU
-    const dim3 grid(ngrid), block(GEO::WGW * 64);
+    static_assert(Body<DevB, GEO, DT>::IPASS_BYTES == IPASS_BYTES, "ffc_route.h");
+    const BwdRoute r = bwd_route<GEO>(d, true);
+    if (r.err) return ffc_fail(r.err);
+    constexpr int T = GEO::WGW * 64;
     if constexpr (!GEO::OUTER) {
-      using BD = Body<DevB, GEO, DT>;        // inner-only multi-pass form (fft 2048): per-pass tables behind the plan tables
-      const int lds = GEO::LDS_BYTES + (d.c.R > 1 ? d.c.R * BD::IPASS_BYTES : 0);
-      int rc = ffc_set_lds(dkf_kernel_small<GEO, DT>, GEO::LDS_BYTES + 2 * BD::IPASS_BYTES);
-      if (rc) return rc;
-      if (d.c.R > 1 && GEO::N != 1024) return ffc_fail("multi-pass plan on a geometry without multi-pass kernels");
-      hipLaunchKernelGGL((dkf_kernel_small<GEO, DT>), grid, block, lds, st, d);
+      return ffc_launch(dkf_kernel_small<GEO, DT>, "dkf_kernel", r.grid, T, r.lds_max, r.lds, st, d);
     } else {
-      const bool half = (GEO::N1 / 2) * GEO::Mi >= d.c.L;
-      if (half) {
-        {
-          int rc = ffc_set_lds(dkf_kernel<GEO, DT, true>, GEO::LDS_BYTES);
-          if (rc) return rc;
-          hipLaunchKernelGGL((dkf_kernel<GEO, DT, true>), grid, block, GEO::LDS_BYTES, st, d);
-        }
-      } else {
-        int rc = ffc_set_lds(dkf_kernel<GEO, DT, false>, GEO::LDS_BYTES);
-        if (rc) return rc;
-        hipLaunchKernelGGL((dkf_kernel<GEO, DT, false>), grid, block, GEO::LDS_BYTES, st, d);
-      }
+      return pick([&](auto mp, auto half) -> int {
+        constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value;
+        if constexpr (!MP) return ffc_launch(dkf_kernel<GEO, DT, HALF>, "dkf_kernel", r.grid, T, r.lds_max, r.lds, st, d);
+        else if constexpr (GEO::N == 32768) return ffc_launch(dkf_rp_kernel<GEO, DT, HALF>, "dkf_rp_kernel", r.grid, T, r.lds_max, r.lds, st, d);
+        else return ffc_fail("internal: the backward route names a kernel that does not exist");
+      }, r.multi_pass, r.half);
     }
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : ffc_fail(std::string("dkf_kernel launch: ") + hipGetErrorString(e));
   }
 };
 
@@ -95,7 +65,7 @@ extern "C" int64_t ffc_dkf_workspace_bytes(const ffc_plan* p, int64_t B, int64_t
   int nchunk, ppc;
   ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc);
   int upw = 8 / p->hp.NW;
-  int64_t slabs = (int64_t)nchunk * ffc_slabs_per_chunk(p) * H * p->hp.R * p->hp.NT * 2048 * 4;   // rows (head, pass)
+  int64_t slabs = (int64_t)nchunk * H * p->hp.R * p->hp.NT * 2048 * 4;   // one fp32 slab per chunk, rows (head, pass)
   // + spectrum scratch: one dtype-complex slot of the fused kernel's size per (workgroup, unit) of the grid
   int64_t hpad = (H + 7) & ~(int64_t)7;
   int64_t zs = p->hp.N1 > 1 ? hpad * nchunk * upw * (int64_t)(p->hp.N / p->hp.R) * 4 : 0;
@@ -106,7 +76,7 @@ extern "C" int64_t ffc_dkf_slab_count(const ffc_plan* p, int64_t B, int64_t H) {
   if (!p) return 0;
   int nchunk, ppc;
   ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc);
-  return (int64_t)nchunk * ffc_slabs_per_chunk(p);
+  return nchunk;      // every geometry reduces its units inside the workgroup and writes one slab per chunk
 }
 extern "C" int ffc_conv_bwd_dkf(const ffc_plan* p, const void* dout, const void* u, const void* pregate, const void* postgate,
                                 void* ws, int64_t B, int64_t H, int64_t L, void* stream) {

@@ -18,6 +18,7 @@
 #include "ffc_body.h"
 #include "ffc_modes.h"
 #include "ffc_big.h"
+#include "ffc_route.h"
 
 namespace ffc {
 
@@ -331,165 +332,121 @@ static void run_wg(int nwaves, int lds_bytes, F fn) {
   pthread_barrier_destroy(&ctx.bar);
 }
 
-// SB: SimB, or SimBA for the forward with an addend (ffcsim_conv_fwd_res; no k -> k_f step and no frequency-sparse form there)
-template <class GEO, int DT, class SB = SimB>
-static void sim_conv_t(const ConvArgs& a) {
-  for (int h = 0; h < a.H; h++)
-    for (int c = 0; c < a.nchunk; c++) {
-      if constexpr (GEO::N == 32768) {
-        if (a.R > 1) {       // mirrors conv_kernel<..., RP = true>: the passes run one after the other in the same workgroup
-          run_wg(GEO::WGW, GEO::LDS_BYTES, [&]() {
-            Body<SB, GEO, DT>::setup_tables(a.tab, a.t);
-            if (a.zsave) {      // conv_rp_kernel<.., SZ> (ffcsim_conv_fwd_res only: ffcsim_conv_fwd passes no spectrum buffer here)
-              if (16 * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv_job<true, true, true>(a, h, c);
-              else Body<SB, GEO, DT>::template conv_job<false, true, true>(a, h, c);
-              return;
-            }
-            if (16 * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv_job<true, true>(a, h, c);
-            else Body<SB, GEO, DT>::template conv_job<false, true>(a, h, c);
-          });
-          continue;
-        }
-      }
-      if constexpr (GEO::N == 1024) {
-        if (a.R > 1) {       // inner-only multi-pass form (fft 2048)
-          run_wg(GEO::WGW, GEO::LDS_BYTES + a.R * Body<SB, GEO, DT>::IPASS_BYTES, [&]() {
-            Body<SB, GEO, DT>::setup_tables(a.tab, a.t);
-            Body<SB, GEO, DT>::setup_tables_ipass(a.tab, a.t, a.R);
-            if (a.zsave || a.yraw) Body<SB, GEO, DT>::template conv_job<false, true, true>(a, h, c);      // conv_rp_kernel<.., SZ>
-            else Body<SB, GEO, DT>::template conv_job<false, true>(a, h, c);
-          });
-          continue;
-        }
-      }
-      run_wg(GEO::WGW, GEO::LDS_BYTES, [&]() {
-        if constexpr (GEO::HAS_SP && !SB::HAS_ADD) {      // frequency-sparse variant (ffc_conv_fwd_sparse)
-          if (a.sparse) {
-            if ((GEO::N1 / 2) * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv<true, false, true>(a, h, c);
-            else Body<SB, GEO, DT>::template conv<false, false, true>(a, h, c);
-            return;
-          }
-        }
-        if constexpr (GEO::OUTER && GEO::NW > 1 && !SB::HAS_ADD) {
-          if (a.kfuse_k || a.kfuse_x) {   // k -> k_f of this head inside the same workgroup (conv_kernel, ConvArgs::kfuse_k / kfuse_x)
-            Body<SB, GEO, DT>::setup_tables(a.tab, a.t);
-            Modes<SB, GEO, DT>::kfft_head(a, h);
-            const bool half = (GEO::N1 / 2) * GEO::Mi >= a.L;
-            if (a.zsave) { if (half) Body<SB, GEO, DT>::template conv_job<true, false, true>(a, h, c); else Body<SB, GEO, DT>::template conv_job<false, false, true>(a, h, c); }
-            else { if (half) Body<SB, GEO, DT>::template conv_job<true>(a, h, c); else Body<SB, GEO, DT>::template conv_job<false>(a, h, c); }
-            return;
-          }
-        }
-        if constexpr (GEO::OUTER) {       // the launcher's HALF variant
-          if (a.zsave) {                  // spectrum-saving training forward (ffc_conv_fwd_z)
-            if ((GEO::N1 / 2) * GEO::Mi >= a.L) Body<SB, GEO, DT>::template conv<true, true>(a, h, c);
-            else Body<SB, GEO, DT>::template conv<false, true>(a, h, c);
-            return;
-          }
-          if ((GEO::N1 / 2) * GEO::Mi >= a.L) { Body<SB, GEO, DT>::template conv<true>(a, h, c); return; }
-        } else {
-          // single-tile sizes: the training forward that keeps the spectra and / or the output before the postgate (conv_kernel<.., SZ>)
-          if (a.zsave || a.yraw) { Body<SB, GEO, DT>::template conv<false, true>(a, h, c); return; }
-        }
-        Body<SB, GEO, DT>::conv(a, h, c);
-      });
-    }
+// Every runner below asks the library's launch rules (ffc_route.h) which instantiation a call takes and runs that one, one workgroup
+// per (head, chunk) job.  -8: the library has no kernel for the call.
+static constexpr int NO_KERNEL = -8;
+// LDS of the backward-side runners: the single-tile sizes with room for the per-pass tables of fft 2048
+template <class GEO> constexpr int sim_lds() { return GEO::LDS_BYTES + (GEO::OUTER ? 0 : 4 * IPASS_BYTES); }
+// job(h, c) as one workgroup of 8 waves per (head, chunk)
+template <class F>
+static int sim_jobs(int H, int nchunk, int lds, F job) {
+  for (int h = 0; h < H; h++)
+    for (int c = 0; c < nchunk; c++) run_wg(8, lds, [&]() { job(h, c); });
+  return 0;
 }
 
+// SB: SimB (conv_kernel / conv_rp_kernel), or SimBA for the forward with an addend (conv_res_kernel / conv_res_rp_kernel)
+template <class GEO, int DT, class SB = SimB>
+static int sim_conv_t(const ConvArgs& a) {
+  using BD = Body<SB, GEO, DT>;
+  static_assert(BD::IPASS_BYTES == IPASS_BYTES && GEO::WGW == 8, "ffc_route.h");
+  const FwdRoute r = fwd_route<GEO>(a);
+  if (r.err) return NO_KERNEL;
+  return pick([&](auto mp, auto half, auto sz, auto sp) -> int {
+    constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value, SZ = decltype(sz)::value, SP = decltype(sp)::value;
+    if constexpr (!fwd_kernel_exists<GEO>(SB::HAS_ADD, MP, HALF, SZ, SP)) {
+      return NO_KERNEL;
+    } else if constexpr (MP) {      // the passes run one after the other in the same workgroup
+      return sim_jobs(a.H, a.nchunk, r.lds, [&](int h, int c) {
+        BD::setup_tables(a.tab, a.t);
+        if constexpr (!GEO::OUTER) BD::setup_tables_ipass(a.tab, a.t, a.R);
+        BD::template conv_job<HALF, true, SZ>(a, h, c);
+      });
+    } else {
+      return sim_jobs(a.H, a.nchunk, r.lds, [&](int h, int c) {
+        if constexpr (GEO::OUTER && GEO::NW > 1 && !SP && !SB::HAS_ADD) {
+          if (a.kfuse_k || a.kfuse_x) {   // k -> k_f of this head inside the same workgroup (ConvArgs::kfuse_k / kfuse_x)
+            BD::setup_tables(a.tab, a.t);
+            Modes<SB, GEO, DT>::kfft_head(a, h);
+            BD::template conv_job<HALF, false, SZ>(a, h, c);
+            return;
+          }
+        }
+        BD::template conv<HALF, SZ, SP>(a, h, c);
+      });
+    }
+  }, r.multi_pass, r.half, r.sz, r.sp);
+}
+
+// FN<Geo, DT>::run(args...) of the fft size and dtype (ffc::with_geo holds the table); -1: unsupported size
 template <template <class, int> class FN, class... A>
 static int dispatch(int N, int dtype, A&&... args) {
-#define FFC_CASE(NN, a, b, c)                                                     \
-  case NN:                                                                        \
-    if (dtype == DT_BF16) FN<Geo<a, b, c>, DT_BF16>::run(args...);                \
-    else FN<Geo<a, b, c>, DT_F16>::run(args...);                                  \
-    return 0;
-  switch (N) {
-    FFC_CASE(256, 1, 16, 16)
-    FFC_CASE(512, 1, 16, 32)
-    FFC_CASE(1024, 1, 32, 32)
-    FFC_CASE(2048, 1, 32, 32)
-    FFC_CASE(4096, 16, 16, 16)
-    FFC_CASE(8192, 32, 16, 16)
-    FFC_CASE(16384, 16, 32, 32)
-    FFC_CASE(32768, 32, 32, 32)
-    FFC_CASE(65536, 32, 32, 32)       // multi-pass sizes: R passes of the 32768 kernel (HostPlan::R, struct Pass)
-    FFC_CASE(131072, 32, 32, 32)
-  }
-#undef FFC_CASE
-  return -1;
+  int rc = 0;
+  const bool found = with_geo(N, [&](auto geo) {
+    using GEO = decltype(geo);
+    rc = dtype == DT_BF16 ? FN<GEO, DT_BF16>::run(args...) : FN<GEO, DT_F16>::run(args...);
+  });
+  return found ? rc : -1;
 }
-template <class GEO, int DT> struct ConvRun { static void run(const ConvArgs& a) { sim_conv_t<GEO, DT>(a); } };
-template <class GEO, int DT> struct ConvResRun { static void run(const ConvArgs& a) { sim_conv_t<GEO, DT, SimBA>(a); } };
+template <class GEO, int DT> struct ConvRun { static int run(const ConvArgs& a) { return sim_conv_t<GEO, DT>(a); } };
+template <class GEO, int DT> struct ConvResRun { static int run(const ConvArgs& a) { return sim_conv_t<GEO, DT, SimBA>(a); } };
 template <class GEO, int DT> struct KfRun {
-  static void run(const KfArgs& a) {
+  static int run(const KfArgs& a) {
     const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
     for (int wg = 0; wg < (nunits + GEO::UPW - 1) / GEO::UPW; wg++)
-      run_wg(GEO::WGW, GEO::LDS_BYTES + (GEO::OUTER ? 0 : 4 * Body<SimB, GEO, DT>::IPASS_BYTES), [&]() { Modes<SimB, GEO, DT>::kfft(a, wg); });
+      run_wg(GEO::WGW, sim_lds<GEO>(), [&]() { Modes<SimB, GEO, DT>::kfft(a, wg); });
+    return 0;
   }
 };
-template <class GEO, int DT> struct DkfRun {
-  static void run(const DkfArgs& d) {
-    for (int h = 0; h < d.c.H; h++)
-      for (int c = 0; c < d.c.nchunk; c++)
-        run_wg(GEO::WGW, GEO::LDS_BYTES + (GEO::OUTER ? 0 : 4 * Body<SimB, GEO, DT>::IPASS_BYTES), [&]() {
-          if constexpr (GEO::N == 32768) {
-            if (d.c.R > 1) {
-              Modes<SimBO, GEO, DT>::BD::setup_tables(d.c.tab, d.c.t);
-              const bool half = 16 * GEO::Mi >= d.c.L;
-              for (int k0 = 0; k0 < d.c.R; k0++) {
-                if (half) Modes<SimBO, GEO, DT>::template dkf<true, true>(d, h, c, h * d.c.nchunk + c, k0, SimBO::wave());
-                else Modes<SimBO, GEO, DT>::template dkf<false, true>(d, h, c, h * d.c.nchunk + c, k0, SimBO::wave());
-              }
-              return;
-            }
+// dkf = true: dkf_kernel / dkf_rp_kernel / dkf_kernel_small; false: bwd_kernel / bwd_rp_kernel / bwd_kernel_small (the library runs the
+// saved-spectra form of the fused sizes as its own instantiation, ZM = 1: ffc_k_bwdz.hip)
+template <class GEO, int DT, bool DKF>
+static int sim_bwd_t(const DkfArgs& d) {
+  using MO = Modes<SimBO, GEO, DT>;
+  const BwdRoute r = bwd_route<GEO>(d, DKF);
+  if (r.err) return NO_KERNEL;
+  const int H = d.c.H, nchunk = d.c.nchunk, lds = sim_lds<GEO>();
+  return pick([&](auto mp, auto half, auto fastk, auto zm) -> int {
+    constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value, FASTK = decltype(fastk)::value, ZM = decltype(zm)::value;
+    if constexpr (!GEO::OUTER) {       // single-tile kernels: one instantiation, saved spectra decided at run time
+      if constexpr (MP || HALF || FASTK || ZM) return NO_KERNEL;
+      else if constexpr (DKF) return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::dkf(d, h, c, h * nchunk + c); });
+      else return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::bwd(d, h, c, h * nchunk + c); });
+    } else if constexpr (MP) {
+      if constexpr (GEO::N != 32768 || (DKF && (FASTK || ZM))) {
+        return NO_KERNEL;
+      } else {
+        using MK = Modes<typename std::conditional<FASTK, SimBOF, SimBO>::type, GEO, DT>;
+        return sim_jobs(H, nchunk, lds, [&](int h, int c) {
+          MK::BD::setup_tables(d.c.tab, d.c.t);
+          for (int k0 = 0; k0 < d.c.R; k0++) {
+            if constexpr (DKF) MK::template dkf<HALF, true>(d, h, c, h * nchunk + c, k0, SimBO::wave());
+            else MK::template bwd<HALF, true>(d, h, c, h * nchunk + c, k0, SimBO::wave());
           }
-          if constexpr (GEO::OUTER) {     // the launcher's HALF variant (L <= N/2)
-            if ((GEO::N1 / 2) * GEO::Mi >= d.c.L) { Modes<SimBO, GEO, DT>::template dkf<true>(d, h, c, h * d.c.nchunk + c); return; }
-          }
-          Modes<SimBO, GEO, DT>::dkf(d, h, c, h * d.c.nchunk + c);
         });
-  }
-};
-template <class GEO, int DT> struct BwdRun {
-  static void run(const DkfArgs& d) {
-    for (int h = 0; h < d.c.H; h++)
-      for (int c = 0; c < d.c.nchunk; c++)
-        run_wg(GEO::WGW, GEO::LDS_BYTES + (GEO::OUTER ? 0 : 4 * Body<SimB, GEO, DT>::IPASS_BYTES), [&]() {
-          if constexpr (GEO::N == 32768) {
-            if (d.c.R > 1) {
-              Modes<SimBO, GEO, DT>::BD::setup_tables(d.c.tab, d.c.t);
-              const bool half = 16 * GEO::Mi >= d.c.L;
-              for (int k0 = 0; k0 < d.c.R; k0++) {
-                if (d.c.fast && (FFC_RP_FASTK != 0)) {      // the launcher's fast-only kernel (bwd_rp_kernel<.., FASTK = true>)
-                  if (half) Modes<SimBOF, GEO, DT>::template bwd<true, true>(d, h, c, h * d.c.nchunk + c, k0, SimBO::wave());
-                  else Modes<SimBOF, GEO, DT>::template bwd<false, true>(d, h, c, h * d.c.nchunk + c, k0, SimBO::wave());
-                } else if (half) Modes<SimBO, GEO, DT>::template bwd<true, true>(d, h, c, h * d.c.nchunk + c, k0, SimBO::wave());
-                else Modes<SimBO, GEO, DT>::template bwd<false, true>(d, h, c, h * d.c.nchunk + c, k0, SimBO::wave());
-              }
-              return;
-            }
-          }
-          if constexpr (GEO::OUTER) {
-            // (the library's launcher runs the saved-spectra form as its own instantiation, ZM = 1: ffc_k_bwdz.hip)
-            if (d.zin) {
-              if ((GEO::N1 / 2) * GEO::Mi >= d.c.L) Modes<SimBO, GEO, DT>::template bwd<true, false, true, 1>(d, h, c, h * d.c.nchunk + c);
-              else Modes<SimBO, GEO, DT>::template bwd<false, false, true, 1>(d, h, c, h * d.c.nchunk + c);
-              return;
-            }
-            if ((GEO::N1 / 2) * GEO::Mi >= d.c.L) { Modes<SimBO, GEO, DT>::template bwd<true>(d, h, c, h * d.c.nchunk + c); return; }
-          }
-          Modes<SimBO, GEO, DT>::bwd(d, h, c, h * d.c.nchunk + c);
-        });
-  }
-};
+      }
+    } else if constexpr (FASTK || (DKF && ZM)) {
+      return NO_KERNEL;
+    } else if constexpr (DKF) {
+      return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template dkf<HALF>(d, h, c, h * nchunk + c); });
+    } else if constexpr (ZM) {
+      return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template bwd<HALF, false, true, 1>(d, h, c, h * nchunk + c); });
+    } else {
+      return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template bwd<HALF>(d, h, c, h * nchunk + c); });
+    }
+  }, r.multi_pass, r.half, r.fastk, !DKF && GEO::OUTER && !r.multi_pass && d.zin != nullptr);
+}
+template <class GEO, int DT> struct DkfRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, true>(d); } };
+template <class GEO, int DT> struct BwdRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, false>(d); } };
 template <class GEO, int DT> struct DkRun {
-  static void run(const DkArgs& a) {
+  static int run(const DkArgs& a) {
     const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
     for (int wg = 0; wg < (nunits + GEO::UPW - 1) / GEO::UPW; wg++)
-      run_wg(GEO::WGW, GEO::LDS_BYTES + (GEO::OUTER ? 0 : 4 * Body<SimB, GEO, DT>::IPASS_BYTES), [&]() { Modes<SimB, GEO, DT>::dkifft(a, wg); });
+      run_wg(GEO::WGW, sim_lds<GEO>(), [&]() { Modes<SimB, GEO, DT>::dkifft(a, wg); });
+    return 0;
   }
 };
-template <class GEO, int DT> struct UpwGet { static void run(int* out) { *out = GEO::UPW; } };
+template <class GEO, int DT> struct UpwGet { static int run(int* out) { *out = GEO::UPW; return 0; } };
 
 }  // namespace ffc
 
@@ -573,10 +530,11 @@ int ffcsim_conv_fwd(int N, int dtype, const void* u, const void* kf, const void*
   a.sparse = g_sparse_rows;
   if (p.N1 > 1 && p.R == 1) { a.zsave = g_z; a.yraw = g_z ? g_yraw : nullptr; }
   if (p.N1 <= 1) { a.zsave = g_z; a.yraw = g_yraw; }      // single-tile sizes: either one alone too (conv_fwd_impl)
-  if (g_kfuse_x && N >= 8192 && N <= 32768 && !a.sparse) {
+  const bool kfuse = fwd_takes_kfft(p, a.nchunk, a.sparse, 0);      // the library's rule for k -> k_f inside the launch
+  if (g_kfuse_x && kfuse) {
     a.kfuse_x = g_kfuse_x; a.kfuse_scale = g_kfuse_xscale; a.kfuse_Lk = N; a.kfuse_fast = 1;
   }
-  if (g_kfuse_k && N >= 8192 && N <= 32768 && !a.sparse) {
+  if (g_kfuse_k && kfuse) {
     a.kfuse_k = g_kfuse_k; a.kfuse_Lk = g_kfuse_lk; a.kfuse_scale = (float)(p.s_k / p.s_fwd) / (dtype == DT_F16 ? 256.f : 1.f); a.kfuse_fast = (g_kfuse_lk % 4 == 0) && !g_force_slow;
   }
   return dispatch<ConvRun>(N, dtype, a);
@@ -614,27 +572,53 @@ int ffcsim_conv_fwd_res(int N, int dtype, const void* u, const void* kf, const v
 }
 
 
-// the library's rule for the long side (ffc_k_big.hip set_long_side): batch pitches in elements, 0 = contiguous, of `in` (fwd) / `out` (inverse)
-// and of the gate; 16-byte accesses need rows of a multiple of 8, 16-byte aligned base pointers and pitches that are multiples of 8
-static int set_long_side(BigArgs* a, int fwd, int Hin, int Llong, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
-  const int64_t hl = (int64_t)Hin * Llong;
-  if ((fwd ? pitch_out : pitch_in) != 0) return -7;
-  int64_t pl = fwd ? pitch_in : pitch_out, pg = a->gate ? pitch_gate : 0;
-  const bool strided = pl || pg;
-  if (!pl) pl = hl;
-  if (!pg) pg = hl;
-  if (pl < hl || pg < hl || (a->lf32 && pl != hl)) return -7;
-  a->pin = fwd ? pl : 0; a->pout = fwd ? 0 : pl; a->pgate = pg;
-  a->strided = (pl != hl || pg != hl) ? 1 : 0;
-  a->fast = (Llong % 8 == 0) && !g_force_slow && !((pl | pg) & 7);
-  if (strided && (((uintptr_t)a->in | (uintptr_t)a->out | (uintptr_t)a->gate) & 15)) a->fast = 0;     // (the contiguous entry points keep taking any host pointer)
-  return 0;
-}
 
 // HBM-level outer pass (ffc_big.h).  fwd: in = long side (Bp_valid rows, Hin, Llong), out = (2*npair, Hin*N0, Mi).
 // *_strided: with the batch pitches of the long-side operands (ffc_outer_pass*_strided), on the same kernel body.
+// What the level runners fill alike, by the library's rules (ffc_route.h decode_dtype / set_level): -1 bad dtype flags, -4 half rows with
+// more than one row per head, -5 no length, -7 long side.  Simulator-side: the contiguous entry points (no pitch given) take any host pointer,
+// so there the long side is judged before the pointers are filled in; g_force_slow takes the 16-byte accesses away.
+static int sim_level_args(BigArgs* a, int* dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair, int Hin, int Mi,
+                          int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
+  *dtype = decode_dtype(*dtype, fwd, a);
+  if (*dtype < 0) return -1;
+  if (!half_rows_ok(*a, Bp_valid, npair)) return -4;
+  if (Llong <= 0) return -5;
+  if (pitch_in || pitch_out || (gate && pitch_gate)) { a->in = in; a->out = out; a->gate = gate; }
+  const bool bad = set_level(a, fwd, Bp_valid, npair, Hin, Mi, Llong, scale, pitch_in, pitch_out, pitch_gate) != nullptr;
+  a->in = in; a->out = out; a->gate = gate;
+  if (bad) return -7;
+  if (g_force_slow) a->fast = 0;
+  return 0;
+}
+// R > 1: pass c of a factor R * 32 (ffc_outer_pass_r; tables of the R-pass plan of the fused 32768 kernel)
 int ffcsim_big_outer_r_strided(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
-                               int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate);
+                               int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
+  HostPlan p;
+  if (R > 1 && N0 != 32) return -3;
+  BigArgs a{};
+  a.R = R; a.c = c;
+  const int rc = sim_level_args(&a, &dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, pitch_in, pitch_out, pitch_gate);
+  if (!build_plan(R > 1 ? 32768 * R : (N0 == 16 ? 16384 : 32768), dtype, &p)) return -1;   // only for the N0-point operand table
+  if (rc) return rc;
+  a.fmat = p.blob.data() + (R > 1 ? p.tabs.matk[c][fwd ? 0 : 1] : p.tabs.mat[0]);
+  if (Mi % (N0 == 16 ? GeoBig<16>::Mi : GeoBig<32>::Mi)) return -2;
+  // the pipelined form where the library's rule allows it and the test asked for it; here 3 "workgroups" walk the blocks so that every
+  // one of them runs several iterations
+  const bool pipe = level_pipe(a, fwd != 0, g_big_pipe != 0);
+  return level_dispatch(N0, dtype == DT_F16, fwd != 0, [&](auto n0, auto dt, auto fw) -> int {
+    constexpr int NN = decltype(n0)::value, DD = decltype(dt)::value;
+    constexpr bool FF = decltype(fw)::value;
+    const int nblk = (int)level_blocks(a, GeoBig<NN>::Mi), npw = pipe ? (nblk < 3 ? nblk : 3) : nblk;
+    for (int wg = 0; wg < npw; wg++)
+      run_wg(GeoBig<NN>::WGW + (pipe ? 1 : 0), pipe ? BigBody<SimB, NN, DD>::PIPE_LDS : GeoBig<NN>::LDS_BYTES, [&]() {
+        if (pipe) BigBody<SimB, NN, DD>::template run_pipe<FF>(a, wg, npw);
+        else if (a.strided) BigBody<SimB, NN, DD, true>::template run<FF>(a, wg);
+        else BigBody<SimB, NN, DD>::template run<FF>(a, wg);
+      });
+    return 0;
+  });
+}
 int ffcsim_big_outer_r(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
                        int Hin, int Mi, int Llong, float scale) {
   return ffcsim_big_outer_r_strided(N0, R, c, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, 0, 0, 0);
@@ -647,96 +631,80 @@ int ffcsim_big_outer_strided(int N0, int dtype, int fwd, const void* in, void* o
                              int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
   return ffcsim_big_outer_r_strided(N0, 1, 0, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, pitch_in, pitch_out, pitch_gate);
 }
-// R > 1: pass c of a factor R * 32 (ffc_outer_pass_r; tables of the R-pass plan of the fused 32768 kernel)
-int ffcsim_big_outer_r_strided(int N0, int R, int c, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
-                               int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
-  HostPlan p;
-  if (R > 1 && N0 != 32) return -3;
-  // the library's dtype flags (ffc_k_big.hip decode_dtype): | 16 = fp32 long side, bits 8..15 = log2 of the forward prescale
-  const int lf32 = (dtype & 16) ? 1 : 0;
-  const int half = (dtype & 32) ? 1 : 0;      // FFC_HALF_ROWS (BigArgs::half)
-  const float lpre = (float)(1u << ((dtype >> 8) & 0xff));
-  dtype &= 15;
-  if (!build_plan(R > 1 ? 32768 * R : (N0 == 16 ? 16384 : 32768), dtype, &p)) return -1;   // only for the N0-point operand table
-  if (half && (Bp_valid != 1 || npair != 1)) return -4;
-  BigArgs a{};
-  a.R = R; a.c = c;
-  a.lf32 = lf32; a.lpre = lpre; a.half = half;
-  a.in = in; a.out = out; a.gate = gate; a.fmat = p.blob.data() + (R > 1 ? p.tabs.matk[c][fwd ? 0 : 1] : p.tabs.mat[0]);
-  a.Bp_valid = Bp_valid; a.npair = npair; a.Hin = Hin; a.Mi = Mi; a.Llong = Llong; a.scale = scale;
-  if (int rc = set_long_side(&a, fwd, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return rc;
-  const int cols = N0 == 16 ? GeoBig<16>::Mi : GeoBig<32>::Mi;
-  if (Mi % cols) return -2;
-  const int nwg = npair * Hin * (Mi / cols);
-  // the launcher's rule (ffc_k_big.hip launch_level): persistent double-buffered form for plain levels with 16-byte accesses and no
-  // input gate; here 3 "workgroups" walk the blocks so that every one of them runs several iterations
-  const bool pipe = g_big_pipe && R == 1 && a.fast && !a.lf32 && !a.half && !a.strided && !(fwd && gate);
-  const int npw = pipe ? (nwg < 3 ? nwg : 3) : nwg;
-  for (int wg = 0; wg < npw; wg++) {
-#define FFC_BIG(NN, DD, FF) run_wg(GeoBig<NN>::WGW + (pipe ? 1 : 0), pipe ? BigBody<SimB, NN, DD>::PIPE_LDS : GeoBig<NN>::LDS_BYTES, [&]() { \
-      if (pipe) BigBody<SimB, NN, DD>::template run_pipe<FF>(a, wg, npw); \
-      else if (a.strided) BigBody<SimB, NN, DD, true>::template run<FF>(a, wg); else BigBody<SimB, NN, DD>::template run<FF>(a, wg); })
-    if (N0 == 16) { if (dtype == DT_BF16) { if (fwd) FFC_BIG(16, DT_BF16, true); else FFC_BIG(16, DT_BF16, false); }
-                    else { if (fwd) FFC_BIG(16, DT_F16, true); else FFC_BIG(16, DT_F16, false); } }
-    else { if (dtype == DT_BF16) { if (fwd) FFC_BIG(32, DT_BF16, true); else FFC_BIG(32, DT_BF16, false); }
-           else { if (fwd) FFC_BIG(32, DT_F16, true); else FFC_BIG(32, DT_F16, false); } }
-#undef FFC_BIG
-  }
-  return 0;
-}
 
-// all R passes in one workgroup run (ffc_outer_pass_all, BigBody::run_all)
+// all R passes in one workgroup run (ffc_outer_pass_all, BigBody::run_all; the wide form BigBody::run_wide beyond the first 32 rows)
 int ffcsim_big_outer_all_strided(int R, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
-                                 int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate);
+                                 int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
+  HostPlan p;
+  BigArgs a{};
+  a.R = R; a.c = 0;
+  const int rc = sim_level_args(&a, &dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, pitch_in, pitch_out, pitch_gate);
+  if (R < 2 || R > 4 || !build_plan(32768 * R, dtype, &p)) return -1;
+  if (rc) return rc;
+  for (int c = 0; c < R; c++) a.fmats[c] = p.blob.data() + p.tabs.matk[c][fwd ? 0 : 1];
+  a.fmat = a.fmats[0];
+  if (Mi % GeoBig<32>::Mi) return -2;
+  if (Llong > R * 32 * Mi) return -5;
+  if (level_wide(a)) {
+    BigArgs w = a;
+    w.strided = 0;
+    if (level_wide_check(w)) return -6;
+    if (pitch_in || pitch_out || pitch_gate) return -7;      // contiguous long side only, as in the library
+    a.wide = 1;
+  }
+  return level_dispatch(32, dtype == DT_F16, fwd != 0, [&](auto n0, auto dt, auto fw) -> int {
+    constexpr int DD = decltype(dt)::value;
+    constexpr bool FF = decltype(fw)::value;
+    if constexpr (decltype(n0)::value != 32) return -3;
+    const int nblk = (int)level_blocks(a, a.wide ? level_wide_cols(a.R) : GeoBig<32>::Mi);
+    for (int wg = 0; wg < nblk; wg++)
+      run_wg(GeoBig<32>::WGW, GeoBig<32>::LDS_BYTES, [&]() {
+        if (a.wide) BigBody<SimB, 32, DD>::template run_wide<FF>(a, wg);
+        else if (a.strided) BigBody<SimB, 32, DD, true>::template run_all<FF>(a, wg);
+        else BigBody<SimB, 32, DD>::template run_all<FF>(a, wg);
+      });
+    return 0;
+  });
+}
 int ffcsim_big_outer_all(int R, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
                          int Hin, int Mi, int Llong, float scale) {
   return ffcsim_big_outer_all_strided(R, dtype, fwd, in, out, gate, Bp_valid, npair, Hin, Mi, Llong, scale, 0, 0, 0);
 }
-int ffcsim_big_outer_all_strided(int R, int dtype, int fwd, const void* in, void* out, const void* gate, int Bp_valid, int npair,
-                                 int Hin, int Mi, int Llong, float scale, int64_t pitch_in, int64_t pitch_out, int64_t pitch_gate) {
-  HostPlan p;
-  const int lf32 = (dtype & 16) ? 1 : 0;
-  const int half = (dtype & 32) ? 1 : 0;
-  const float lpre = (float)(1u << ((dtype >> 8) & 0xff));
-  dtype &= 15;
-  if (R < 2 || R > 4 || !build_plan(32768 * R, dtype, &p)) return -1;
-  if (half && (Bp_valid != 1 || npair != 1)) return -4;
-  BigArgs a{};
-  a.R = R; a.c = 0;
-  a.lf32 = lf32; a.lpre = lpre; a.half = half;
-  a.in = in; a.out = out; a.gate = gate;
-  for (int c = 0; c < R; c++) a.fmats[c] = p.blob.data() + p.tabs.matk[c][fwd ? 0 : 1];
-  a.fmat = a.fmats[0];
-  a.Bp_valid = Bp_valid; a.npair = npair; a.Hin = Hin; a.Mi = Mi; a.Llong = Llong; a.scale = scale;
-  if (Llong <= 0) return -5;
-  if (int rc = set_long_side(&a, fwd, Hin, Llong, pitch_in, pitch_out, pitch_gate)) return rc;
-  if (Mi % GeoBig<32>::Mi) return -2;
-  if (Llong > R * 32 * Mi) return -5;
-  if (Llong > 32 * Mi) {      // the wide form (ffc_outer_pass_all: long side beyond the first 32 rows, BigBody::run_wide)
-    if (lf32 || half || GeoBig<32>::WGW % R) return -6;
-    if (pitch_in || pitch_out || pitch_gate) return -7;      // contiguous long side only, as in the library
-    a.wide = 1;
-    const int nw = npair * Hin * (Mi / (128 * (GeoBig<32>::WGW / R)));
-    for (int wg = 0; wg < nw; wg++) {
-#define FFC_BIGW(DD, FF) run_wg(GeoBig<32>::WGW, GeoBig<32>::LDS_BYTES, [&]() { BigBody<SimB, 32, DD>::template run_wide<FF>(a, wg); })
-      if (dtype == DT_BF16) { if (fwd) FFC_BIGW(DT_BF16, true); else FFC_BIGW(DT_BF16, false); }
-      else { if (fwd) FFC_BIGW(DT_F16, true); else FFC_BIGW(DT_F16, false); }
-#undef FFC_BIGW
-    }
-    return 0;
-  }
-  const int nwg = npair * Hin * (Mi / GeoBig<32>::Mi);
-  for (int wg = 0; wg < nwg; wg++) {
-#define FFC_BIGA(DD, FF) run_wg(GeoBig<32>::WGW, GeoBig<32>::LDS_BYTES, [&]() { \
-      if (a.strided) BigBody<SimB, 32, DD, true>::template run_all<FF>(a, wg); else BigBody<SimB, 32, DD>::template run_all<FF>(a, wg); })
-    if (dtype == DT_BF16) { if (fwd) FFC_BIGA(DT_BF16, true); else FFC_BIGA(DT_BF16, false); }
-    else { if (fwd) FFC_BIGA(DT_F16, true); else FFC_BIGA(DT_F16, false); }
-#undef FFC_BIGA
-  }
-  return 0;
-}
 
 int ffcsim_upw(int N) { int u = 0; dispatch<UpwGet>(N, 0, &u); return u; }
+
+// The launch rules of ffc_route.h for one call, as ints (tests/test_launch_rules.py holds them against hand-written values).
+// flags: the library's tuning flags (FFC_FLAGS: 32, 64, 128) | 1 << 16: a spectrum buffer is given | 1 << 17: y_raw is given
+// | 1 << 18: frequency-sparse k_f | 1 << 19: the rows take 16-byte accesses (ConvArgs::fast).
+// out[0..7]   forward            {multi_pass, half, sz, sp, grid, lds_max, lds, no kernel}
+// out[8..15]  fused backward     {multi_pass, half, fastk, small, grid, lds_max, lds, no kernel}
+// out[16..23] dk_f accumulation  (as the backward)
+// out[24] k -> k_f inside the forward launch; out[25] / out[26] dk out of the backward launch as real dk / as complex rows (DK_*)
+int ffcsim_launch_route(int N, int dtype, int B, int H, int L, int nchunk, int persist, int flags, int* out) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  static char buf[16];
+  DkfArgs d{};
+  ConvArgs& a = d.c;
+  a.B = B; a.H = H; a.L = L; a.npair = (B + 1) / 2; a.nchunk = nchunk; a.persist = persist; a.R = p.R;
+  a.zsave = (flags & (1 << 16)) ? buf : nullptr; a.yraw = (flags & (1 << 17)) ? buf : nullptr;
+  a.sparse = (flags & (1 << 18)) ? 2 : 0; a.fast = (flags & (1 << 19)) ? 1 : 0;
+  with_geo(N, [&](auto geo) {
+    using GEO = decltype(geo);
+    const FwdRoute f = fwd_route<GEO>(a);
+    const int fo[8] = {f.multi_pass, f.half, f.sz, f.sp, f.grid, f.lds_max, f.lds, f.err != nullptr};
+    memcpy(out, fo, sizeof fo);
+    for (int dkf = 0; dkf < 2; dkf++) {
+      const BwdRoute b = bwd_route<GEO>(d, dkf != 0);
+      const int bo[8] = {b.multi_pass, b.half, b.fastk, b.small, b.grid, b.lds_max, b.lds, b.err != nullptr};
+      memcpy(out + 8 + 8 * dkf, bo, sizeof bo);
+    }
+  });
+  out[24] = fwd_takes_kfft(p, nchunk, a.sparse, flags & 0xffff);
+  out[25] = bwd_dk_form(p, nchunk, flags & 0xffff, false);
+  out[26] = bwd_dk_form(p, nchunk, flags & 0xffff, true);
+  return 0;
+}
 
 int ffcsim_kernel_fft_c(int N, int dtype, const void* xpair, int H, void* kf, float scale) {
   HostPlan p;
@@ -806,14 +774,13 @@ int ffcsim_conv_bwd(int N, int dtype, const void* dout, const void* u, const voi
   if (p.N1 > 1 && p.R == 1 && g_z) { d.zin = g_z; d.yraw = g_yraw; a.flags = g_flags; a.stream = 1; }
   if (p.N1 <= 1) { d.zin = g_z; d.yraw = dpost ? g_yraw : nullptr; }      // (conv_bwd_impl: y_raw with or without the spectra)
   HostPlan pbf;
-  if (g_dk_pair && a.nchunk == 1 && N >= 8192 && N <= 32768) {
-    d.dk_pair = g_dk_pair; d.Lk = N; d.dk_scale = g_dk_pair_scale; d.dk_fast = 1;
+  // the library's rule for dk out of the backward launch, with fft 8192 asked for as tuning flag 128 does
+  if (g_dk_pair && bwd_dk_form(p, a.nchunk, 128, true) != DK_SEPARATE) {
     if (!build_plan(N, DT_BF16, &pbf)) return -1;
-    d.tab_bf = pbf.blob.data(); d.t_bf = pbf.tabs;
-  } else if (g_dk_out && a.nchunk == 1 && ((N >= 8192 && N <= 32768) || (p.R > 1 && p.N1 > 1 && dtype == DT_BF16))) {
-    d.dk_out = g_dk_out; d.Lk = g_dk_lk; d.dk_scale = (float)(1.0 / p.s_fwd); d.dk_fast = (g_dk_lk % 4 == 0) && !g_force_slow;
+    set_dk_tail(&d, nullptr, g_dk_pair, N, g_dk_pair_scale, 1, pbf.blob.data(), pbf.tabs);
+  } else if (g_dk_out && bwd_dk_form(p, a.nchunk, 128, false) != DK_SEPARATE) {
     if (!build_plan(N, DT_BF16, &pbf)) return -1;
-    d.tab_bf = pbf.blob.data(); d.t_bf = pbf.tabs;
+    set_dk_tail(&d, g_dk_out, nullptr, g_dk_lk, (float)(1.0 / p.s_fwd), (g_dk_lk % 4 == 0) && !g_force_slow, pbf.blob.data(), pbf.tabs);
   }
   std::vector<uint8_t> zs((size_t)H * a.nchunk * upw * N * 4 + 16);
   d.zscratch = zs.data();

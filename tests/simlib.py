@@ -12,7 +12,7 @@ DT_BF16, DT_F16 = 0, 1
 def build_sim(force=False):
     so = os.path.join(LIBDIR, "libffcsim.so")
     srcs = [os.path.join(CSRC, f) for f in ("ffc_sim.cpp", "ffc_plan.cpp")]
-    deps = srcs + [os.path.join(CSRC, f) for f in ("ffc_body.h", "ffc_modes.h", "ffc_layout.h", "ffc_plan.h", "ffc_big.h")]
+    deps = srcs + [os.path.join(CSRC, f) for f in ("ffc_body.h", "ffc_modes.h", "ffc_layout.h", "ffc_plan.h", "ffc_big.h", "ffc_route.h")]
     if force or not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         os.makedirs(LIBDIR, exist_ok=True)
         subprocess.check_call(["g++", "-O0",   # one large translation unit: -O1 compiles 7.5 min for a 23 s test run, -O0 50 s for 40 s
@@ -140,7 +140,7 @@ class SimOps:
         if self.half:
             assert bv == 1 and npair == 1
             dt = dt | 32
-        if lf32 is not None:       # the library's dtype flags (csrc/ffc_k_big.hip decode_dtype)
+        if lf32 is not None:       # the library's dtype flags (csrc/ffc_route.h decode_dtype)
             e = int(round(np.log2(lf32)))
             assert 2.0 ** e == lf32 and (inp if fwd else out).dtype == np.float32
             dt = dt | 16 | (e << 8)
