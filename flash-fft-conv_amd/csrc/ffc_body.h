@@ -1426,12 +1426,123 @@ struct Body {
     }
   }
 
+  // Phase C of the half-empty 32-point outer digit (fft 32768, L <= N/2): only the 16 live output rows n1 < 16 are computed, on
+  // v_mfma_f32_16x16x32 (B::mfma16): D rows = n1 (4 per lane), D column = lane % 16, the whole contraction k1 = 0..31 in one
+  // instruction -- 4 MFMAs per column tile where the 32x32x16 forms above run 8 (two K-steps over 32 output rows, 16 of them beyond L),
+  // and a quarter of their accumulator registers, so that one form fits the forward and the backward register budgets.
+  // Lane (c = lane % 16, g = lane / 16): the wave's 128 columns are taken in two halves hc of 64; the lane reads the 8-byte chunk of
+  // columns 64 hc + 4 c .. + 3 (the four column tiles t) of the 8 rows k1 = kslot_row(g / 2, g % 2, e), both planes (32 registers), and
+  // merges one operand dword per two rows and tile as the quad form does.  With that k order the matrix operand of lane (n1 = c, g) is the
+  // 16 bytes that lane n1 + 32 (g % 2) of K-step g / 2 holds in the forward table at L_F1: no table of its own (conjugate: Fi and -Fi
+  // trade places).  The four lane groups read four E rows at the same columns; rows are 2 KB apart, so groups g and g + 1 meet on the
+  // same banks (2-way on 16 ds_read_b64 per half; the swizzle is a function of the column alone.  Measured: 0.3 % of the forward's wave
+  // cycles).
+  // After the 4 tiles a lane owns 4 adjacent columns of rows 4 g + r: one 8-byte word per row and plane.
+  //   GS = false: the word goes to E where outer_stage_quad writes it; rows_out / rows_out_g and everything behind them are unchanged.
+  //   GS = true:  the word goes to the output row itself (plane 0 -> batch row 2 pq, plane 1 -> 2 pq + 1), 16 lanes x 8 bytes = 128
+  //               contiguous bytes per row and instruction; no LDS write, fence, LDS read or rows_out.  Kernels instantiated with it are
+  //               launched for plain rows only: 16-byte-aligned tensors, L % 8 == 0, no output gate / addend / second copy (ffc_route.h).
+  // The K = 32 sum is formed in one instruction, so the last bits may differ from the two-K-step forms; tuning flag 256 keeps those.
+  static constexpr bool HALF_C = GEO::N1 == 32 && GEO::N2 == 32 && GEO::N3 == 32;
+  using A4 = typename B::A4;
+  // mid(): called once the half's LDS reads have returned (its first tile's MFMAs are issued), ahead of the other tiles and the stores
+  struct NoMid { FFC_FN void operator()() const {} };
+  template <bool GS, class MID>
+  static FFC_FN void outer_inv_half_cols(int hc, Unit un, const W4& Cr, const W4& Ci, const W4& Cn, const ConvArgs* a, int h, int pq, MID mid) {
+    const i32 lane = B::opaque(B::lane());
+    const i32 c = lane & 15, g = lane >> 4;
+    const i32 m0 = c * 4 + (hc * 64 + un.wq * 128);
+    const i32 colr = e_off<GEO, i32>((g >> 1) * 16 + (g & 1) * 4, m0) + un.eb;      // row kslot_row(g / 2, g % 2, 0)
+    U2 rawr[8], rawi[8];
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+      i32 off = colr + kslot_row(0, 0, e) * (GEO::Mi * 2);
+      rawr[e] = B::lds_r64(off); rawi[e] = B::lds_r64(off + GEO::PLANE);
+    }
+    A4 re[4], im[4];
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      W4 dr, di;
+#pragma unroll
+      for (int d = 0; d < 4; d++) {
+        const u32 ar = (t & 2) ? rawr[2 * d].y : rawr[2 * d].x, br = (t & 2) ? rawr[2 * d + 1].y : rawr[2 * d + 1].x;
+        const u32 ai = (t & 2) ? rawi[2 * d].y : rawi[2 * d].x, bi = (t & 2) ? rawi[2 * d + 1].y : rawi[2 * d + 1].x;
+        dr[d] = (t & 1) ? B::merge_hi(ar, br) : B::merge_lo(ar, br);
+        di[d] = (t & 1) ? B::merge_hi(ai, bi) : B::merge_lo(ai, bi);
+      }
+      re[t] = B::a4_zero(); im[t] = B::a4_zero();
+      B::template mfma16<DT>(re[t], Cr, dr);
+      B::template mfma16<DT>(im[t], Ci, dr);
+      B::template mfma16<DT>(re[t], Cn, di);
+      B::template mfma16<DT>(im[t], Cr, di);
+      if (t == 0) mid();
+    }
+    U2 wr[4], wi[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      wr[r].x = B::template pack<DT>(re[0][r], re[1][r]); wr[r].y = B::template pack<DT>(re[2][r], re[3][r]);
+      wi[r].x = B::template pack<DT>(im[0][r], im[1][r]); wi[r].y = B::template pack<DT>(im[2][r], im[3][r]);
+    }
+    if constexpr (!GS) {
+      const i32 colw = e_off<GEO, i32>(g * 4, m0) + un.eb;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        B::lds_w64(colw + r * (GEO::Mi * 2), wr[r]);
+        B::lds_w64(colw + (r * (GEO::Mi * 2) + GEO::PLANE), wi[r]);
+      }
+    } else {
+      const i32 n = g * (4 * GEO::Mi) + m0;      // position of row 4 g, column m0 in the output row
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        const int b = 2 * pq + pl;
+        const bool ok = b < a->B;
+        uint16_t* base = (uint16_t*)a->y + row_off(b, ok, a->sby, h, a->L);
+        // (one branch for the four stores of a plane, not one per instruction)
+        if (a->stream) {
+#pragma unroll
+          for (int r = 0; r < 4; r++) B::g_w64_nt(base, (n + r * GEO::Mi) >> 2, pl ? wi[r] : wr[r], ((n + r * GEO::Mi) < a->L) && ok);
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; r++) B::g_w64(base, (n + r * GEO::Mi) >> 2, pl ? wi[r] : wr[r], ((n + r * GEO::Mi) < a->L) && ok);
+        }
+      }
+    }
+  }
+  // last(): called when the stage's last LDS read has returned, under the second half's remaining MFMAs and its stores (the backward on
+  // saved spectra requests the next pair's rows there: E rows 16.. of the wave's slice are dead from that point on)
+  template <bool GS>
+  static FFC_FN void outer_inv_half(Unit un, const ConvArgs* a = nullptr, int h = 0, int pq = 0) { outer_inv_half<GS>(un, a, h, pq, NoMid()); }
+  template <bool GS, class LAST>
+  static FFC_FN void outer_inv_half(Unit un, const ConvArgs* a, int h, int pq, LAST last) {
+    static_assert(HALF_C && GEO::S1 == 1 && GEO::NW == 8, "half-height phase C: fft 32768");
+    static_assert(!GS || !B::HAS_ADD, "the direct store has no addend");
+    const i32 lane = B::opaque(B::lane());
+    const i32 toff = ((lane & 15) + ((lane >> 4) & 1) * 32) * 16 + (lane >> 5) * 3072 + GEO::L_F1;
+    U4 v0 = B::lds_r128(toff), v1 = B::lds_r128(toff + 1024), v2 = B::lds_r128(toff + 2048);
+    W4 Cr = B::w4(v0.x, v0.y, v0.z, v0.w);      // conj F = Fr - i Fi: real part Fr,
+    W4 Ci = B::w4(v2.x, v2.y, v2.z, v2.w);      // imaginary part -Fi (table form 2),
+    W4 Cn = B::w4(v1.x, v1.y, v1.z, v1.w);      // and its negative Fi (form 1), which multiplies the data's imaginary plane into re
+    B::pin(Cr); B::pin(Ci); B::pin(Cn);
+    if constexpr (B::LEAN_OUTER) {
+#pragma unroll 1
+      for (int hc = 0; hc < 2; hc++)      // (a runtime loop bounds the live ranges)
+        outer_inv_half_cols<GS>(hc, un, Cr, Ci, Cn, a, h, pq, [&]() { if (hc == 1) last(); });
+    } else {
+      outer_inv_half_cols<GS>(0, un, Cr, Ci, Cn, a, h, pq, NoMid());
+      outer_inv_half_cols<GS>(1, un, Cr, Ci, Cn, a, h, pq, last);
+    }
+  }
+
   // The forward/dx kernels take the tile-pair variant (fastest); the backward kernels, which run on the
   // architectural half of the register file, take the per-tile one (B::LEAN_OUTER).
   // NOTW: no outer twiddle behind the forward DFT (FFC_FOLD_TW: it is folded into the inner stages' per-tile matrices, tile_fwd<.., FOLD>)
   template <bool FWD, bool HALF, bool RP = false, bool DIN = false, bool NOTW = false>
-  static FFC_FN void outer_stage(int L, Unit un, float s_fwd = 1.0f, Pass ps = Pass()) {
+  static FFC_FN void outer_stage(int L, Unit un, float s_fwd = 1.0f, Pass ps = Pass(), int flags = 0) {
     if constexpr (DIN) { outer_stage_pair<FWD, HALF, RP, true, NOTW>(L, un, s_fwd, ps); return; }
+    // phase C of single-pass fft 32768 at L <= N/2, every kernel: the half-height form into E (tuning flag 256: the forms below)
+    if constexpr (!FWD && HALF && !RP && HALF_C) {
+      if (!(flags & 256)) { outer_inv_half<false>(un); return; }
+    }
     // backward kernels (128-VGPR budget): the tile-pair form only fits with one K-step of raw rows (half-empty outer digit)
     if constexpr (B::LEAN_OUTER && !(FWD && HALF && GEO::N1 == 32)) outer_stage_tile<FWD, HALF, RP, NOTW>(L, un, s_fwd, ps);
     // (HALF kernels only: same box, round 5 -- forward -1 ... -3 % at L <= N/2 (config 2 0.4474 -> 0.4334 ms with the chain change, gated
@@ -2242,8 +2353,10 @@ struct Body {
     if constexpr (GEO::NW > 1) B::barrier();
     else B::lds_fence();
   }
-  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false>
+  // GS: phase C stores the output rows itself (outer_inv_half<true>); instantiated for, and launched on, plain rows only
+  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false>
   static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0) {
+    static_assert(!GS || (HALF && !RP && !SP && HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
     constexpr int NC = HALF ? NCH / 2 : NCH;
     // HALF: the next pair's rows (32 VGPRs) are prefetched behind the last k_f load of phase B, so they
     // arrive during the last tile / phase C / the stores and no earlier in-order vmcnt wait is delayed.
@@ -2360,8 +2473,13 @@ struct Body {
       FFC_TICK(4)
       FFC_PRIO(3)
       if constexpr (PREFETCH) { if (it + 1 < iters && p + GEO::UPW < p1) rows_load<NC>(a, h, p + GEO::UPW, un, X); }
-      if (act) {
-        outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps);
+      if constexpr (GS) {
+        if (act) {
+          outer_inv_half<true>(un, &a, h, p);
+          FFC_TICK(5)
+        }
+      } else if (act) {
+        outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);
         B::lds_fence();
         FFC_TICK(5)
         FFC_PRIO(2)
@@ -2391,13 +2509,13 @@ struct Body {
   // ------------------------------------------------------------------ workgroup entry: conv
   // Workgroup handles head h and one chunk of that head's pairs, UPW units at a time.
   // HALF is chosen by the launcher: 32-point outer digit and L <= N/2
-  template <bool HALF = false, bool SZ = false, bool SP = false>
+  template <bool HALF = false, bool SZ = false, bool SP = false, bool GS = false>
   static FFC_FN void conv(const ConvArgs& a, int h, int chunk) {
     setup_tables(a.tab, a.t);
-    conv_job<HALF, false, SZ, SP>(a, h, chunk);
+    conv_job<HALF, false, SZ, SP, GS>(a, h, chunk);
   }
   // one (head, chunk) job; the tables are already in LDS.  RP: all passes of a multi-pass size
-  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false>
+  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false>
   static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk) {
     const int wv = B::wave();
     Unit un;
@@ -2408,7 +2526,7 @@ struct Body {
     int p1 = p0 + a.ppc;
     if (p1 > a.npair) p1 = a.npair;
     if constexpr (GEO::OUTER) {
-      outer_jobs<HALF, false, RP, SZ, SP>(a, h, p0, p1, u, un);
+      outer_jobs<HALF, false, RP, SZ, SP, GS>(a, h, p0, p1, u, un);
     } else {
       // one tile of G pairs per wave
       const int q0 = p0 / GEO::G, q1 = (p1 + GEO::G - 1) / GEO::G;

@@ -15,6 +15,14 @@ struct T {
     static_assert(Body<DevB, GEO, DT>::IPASS_BYTES == IPASS_BYTES, "ffc_route.h");
     const FwdRoute r = fwd_route<GEO>(a);
     if (r.err) return ffc_fail(r.err);
+    if (r.gs) {      // plain rows of fft 32768 at L <= N/2: the kernels whose phase C stores the rows (FAM::kernel_gs)
+      if constexpr (!FAM::HAS_ADD && GEO::N == 32768)
+        return pick([&](auto sz) -> int {
+          return ffc_launch(FAM::template kernel_gs<GEO, DT, decltype(sz)::value>(), FAM::what(false, decltype(sz)::value, false, true), r.grid, GEO::WGW * 64, r.lds_max, r.lds, st, a);
+        }, r.sz);
+      else
+        return ffc_fail("internal: the forward route names a kernel that does not exist");
+    }
     return pick([&](auto mp, auto half, auto sz, auto sp) -> int {
       constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value, SZ = decltype(sz)::value, SP = decltype(sp)::value;
       if constexpr (fwd_kernel_exists<GEO>(FAM::HAS_ADD, MP, HALF, SZ, SP))

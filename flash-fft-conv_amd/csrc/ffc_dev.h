@@ -25,6 +25,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2v __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 extern __shared__ __attribute__((aligned(16))) uint8_t ffc_smem[];
 
@@ -41,6 +43,7 @@ struct DevB {
   static constexpr bool HAS_ADD = false;       // true (DevBA): the forward's output epilogue adds ConvArgs::addend (ffc_conv_fwd_res)
   using A16 = f32x16;   // 16 consecutive VGPRs/AGPRs: the MFMA accumulator tuple
   using W4 = u32x4v;    // 4 consecutive VGPRs: one MFMA A/B operand
+  using A4 = f32x4;     // 4 consecutive VGPRs: the accumulator tuple of the 16x16x32 MFMA (mfma16)
   static constexpr bool HAS_TR = true;
   // element-wise complex multiply of two accumulator tuples (x (x) t or x (x) conj t): whole-vector fp32 ops,
   // which gfx950 legalises to v_pk_mul_f32 / v_pk_fma_f32 on aligned register pairs
@@ -101,6 +104,7 @@ struct DevB {
   }
   static FFC_FN A16 a16_scale(const A16& a, float s) { return a * s; }
   static FFC_FN A16 a16_zero() { A16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}; return z; }
+  static FFC_FN A4 a4_zero() { A4 z = {0.f, 0.f, 0.f, 0.f}; return z; }
   static FFC_FN W4 w4(u32 a, u32 b, u32 c, u32 e) { W4 v = {a, b, c, e}; return v; }
 
   static FFC_FN i32 lane() { return (int)(threadIdx.x & 63); }
@@ -146,6 +150,8 @@ struct DevB {
     else __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
   }
   static FFC_FN void vm_wait0() { __builtin_amdgcn_s_waitcnt(0x0F70); }      // s_waitcnt vmcnt(0)
+  // s_waitcnt lgkmcnt(0): the wave's LDS reads have returned; the scheduling fence keeps what follows behind it
+  static FFC_FN void lds_wait0() { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); }
   static FFC_FN void lds_w32p(i32 off, u32 v, pred p) { if (p) *(uint32_t*)(ffc_smem + off) = v; }
   static FFC_FN pred pnot(pred p) { return !p; }
   static FFC_FN u32 uconst(uint32_t c) { return c; }
@@ -192,6 +198,9 @@ struct DevB {
   static FFC_FN void g_w64(void* base, i32 o8, U2 v, pred p) {
     if (p) ((uint2*)base)[o8] = make_uint2(v.x, v.y);
   }
+  static FFC_FN void g_w64_nt(void* base, i32 o8, U2 v, pred p) {
+    if (p) { u32x2v t = {v.x, v.y}; __builtin_nontemporal_store(t, ((u32x2v*)base) + o8); }
+  }
   static FFC_FN U4 g_r128(const void* base, i32 o16) {
     uint4 v = ((const uint4*)base)[o16];
     return U4{v.x, v.y, v.z, v.w};
@@ -219,6 +228,15 @@ struct DevB {
       acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
     else
       acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
+  }
+  // v_mfma_f32_16x16x32_{bf16,f16}: D(16 x 16) += A(16 x 32) B(32 x 16).  Lane l holds A[l & 15][8 (l >> 4) + e] and B[8 (l >> 4) + e][l & 15]
+  // in operand element e = 0..7, and D[4 (l >> 4) + r][l & 15] in accumulator register r = 0..3.
+  template <int DT>
+  static FFC_FN void mfma16(A4& acc, const W4& a, const W4& b) {
+    if (DT == DT_BF16)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), acc, 0, 0, 0);
+    else
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), acc, 0, 0, 0);
   }
   template <int DT>
   static FFC_FN u32 pack(f32 lo, f32 hi) {

@@ -4,7 +4,8 @@
 //   N = N1*N2*N3,  n = n1*Mi + n2*N3 + n3 (Mi = N2*N3),  f = k1 + N1*(k2 + N2*k3)
 //   stage order fwd: n1 (outer, strided) -> n2 -> n3 ; inverse: k3 -> k2 -> k1.
 // Every DFT stage is a 32x32 complex tile product on v_mfma_f32_32x32x16_{bf16,f16};
-// 16-point digits are embedded block-diagonally (two independent sub-blocks per tile).
+// 16-point digits are embedded block-diagonally (two independent sub-blocks per tile).  One exception: the outer inverse stage of
+// fft 32768 at L <= N/2 computes its 16 live rows on v_mfma_f32_16x16x32 (ffc_body.h Body::outer_inv_half).
 // The reference's factor tables are flashfftconv/conv.py:72-551 (semantic equivalent).
 #pragma once
 #include <stdint.h>

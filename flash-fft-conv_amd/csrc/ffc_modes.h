@@ -965,8 +965,11 @@ struct Modes : Body<B, GEO, DT> {
   // ZM: 1 = on the spectra the forward pass saved (d.zin), 0 = recomputing, -1 = decided at run time (single-tile kernels).
   // The fused sizes >= 4096 compile the two forms as separate kernels (bwd_kernel<.., ZM>: ffc_k_bwd.hip / ffc_k_bwdz.hip):
   // each carries only its own half of the pair loop, and a profile names them apart.
-  template <bool HALF = false, bool RP = false, bool SETUP = true, int ZM = -1>
+  // GS: the last phase C stores the du rows itself (Body::outer_inv_half<true>): single-pass fft 32768 at L <= N/2 without an input
+  // gate or dpregate, 16-byte rows (ffc::direct_store_ok); the dpost transform of a gated call keeps rows_out (its rows are multiplied)
+  template <bool HALF = false, bool RP = false, bool SETUP = true, int ZM = -1, bool GS = false>
   static FFC_FN void bwd(const DkfArgs& d, int h, int chunk, int wg_linear, int k0 = 0, int wv_in = 0) {
+    static_assert(!GS || (HALF && !RP && BD::HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
     const ConvArgs& a = d.c;
     const Pass ps = RP ? make_pass(a.tab, a.t, a.R, k0) : Pass();
     const int hk = RP ? h * a.R + k0 : h;          // k_f row of this (head, pass)
@@ -1054,7 +1057,7 @@ struct Modes : Body<B, GEO, DT> {
             }
             BD::unit_barrier();
             if (act) {
-              BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps);
+              BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);
               B::lds_fence();
               if constexpr (RP) BD::template rows_out_rp<NCX>(aq, h, p, un, ps);
               else BD::template rows_out<NCX>(aq, h, p, un);
@@ -1109,7 +1112,7 @@ struct Modes : Body<B, GEO, DT> {
           FFC_BPRIO(1)
           if (dpost_tf) {
             if (act) {
-              BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps);
+              BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);
               B::lds_fence();
               if constexpr (RP) BD::template rows_out_rp<NCX>(aq, h, p, un, ps);    // dpost = y * dout
               else BD::template rows_out<NCX>(aq, h, p, un);
@@ -1138,8 +1141,19 @@ struct Modes : Body<B, GEO, DT> {
         }
         BD::unit_barrier();
         FFC_BPRIO(3)
-        if (act) {
-          BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps);
+        if constexpr (GS) {
+          if (act) {
+            // the next pair's dout rows into E rows 16.. of the wave's slice, requested as soon as phase C's last LDS read has returned
+            // (lds_wait0: the copies go through the vector-memory path, which is not ordered behind pending LDS reads): they are in
+            // flight under the second half's MFMAs and the du stores.  Phase C writes nothing to LDS here
+            BD::template outer_inv_half<true>(un, &ao, h, p, [&]() {
+              if constexpr (DMA_OK) {
+                if (dma && p + GEO::UPW < p1) { B::lds_wait0(); BD::rows_dma(ad, h, p + GEO::UPW, un); }
+              }
+            });
+          }
+        } else if (act) {
+          BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);
           B::lds_fence();
           // the next pair's dout rows into E rows 16.. (dead: phase C has read them), in flight under the du stores below
           if constexpr (DMA_OK) { if (dma && p + GEO::UPW < p1) BD::rows_dma(ad, h, p + GEO::UPW, un); }

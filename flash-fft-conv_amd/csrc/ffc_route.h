@@ -59,7 +59,15 @@ struct FwdRoute {
   bool sp;              // SP: frequency-sparse k_f
   int grid, lds_max, lds;      // workgroups, dynamic-LDS limit of the kernel, dynamic LDS of this launch
   const char* err;      // non-null: no kernel for this call
+  bool gs;              // GS: phase C stores the output rows itself (Body::outer_inv_half<true>), see direct_store_ok
 };
+// Where phase C may store its rows straight to global memory: single-pass fft 32768 at L <= N/2, plain output rows -- 16-byte-aligned
+// tensors with L % 8 == 0 (`fast`), and nothing that multiplies, adds to or copies the rows on their way out (`plain`).  Tuning flag 256
+// keeps the earlier stages and rows_out everywhere.
+template <class GEO>
+inline bool direct_store_ok(bool half, bool multi_pass, int fast, bool plain, int flags) {
+  return GEO::N == 32768 && half && !multi_pass && fast && plain && !(flags & 256);
+}
 template <class GEO>
 inline FwdRoute fwd_route(const ConvArgs& a) {
   FwdRoute r{};
@@ -90,6 +98,7 @@ inline FwdRoute fwd_route(const ConvArgs& a) {
   }
   // y_raw without the spectra: the single-tile sizes only
   r.sz = a.zsave || (!GEO::OUTER && a.yraw);
+  r.gs = direct_store_ok<GEO>(r.half, false, a.fast, !a.postgate && !a.addend && !a.yraw, a.flags);
   return r;
 }
 // the forward instantiations that exist (add: the family with an addend in the output epilogue has no frequency-sparse form)
@@ -108,6 +117,7 @@ struct BwdRoute {
   bool small;           // single-tile kernel
   int grid, lds_max, lds;
   const char* err;
+  bool gs;              // bwd_kernel only: the du rows from phase C itself (no input gate, no dpregate), see direct_store_ok
 };
 template <class GEO>
 inline BwdRoute bwd_route(const DkfArgs& d, bool dkf) {
@@ -125,6 +135,7 @@ inline BwdRoute bwd_route(const DkfArgs& d, bool dkf) {
   if (GEO::OUTER) {
     if (GEO::NW == 1 && c.persist > 0 && r.grid > c.persist) r.grid = c.persist;      // persistent: one workgroup per CU (fft 4096)
     r.half = (GEO::N1 / 2) * GEO::Mi >= c.L;
+    r.gs = !dkf && direct_store_ok<GEO>(r.half, false, c.fast, !c.pregate && !d.dpre, c.flags);
     return r;
   }
   r.small = true;

@@ -2,7 +2,7 @@
 // one host thread per wavefront, pthread barrier = s_barrier, a byte array = LDS.
 // TEST INFRASTRUCTURE ONLY (tests/ and __graft_entry__.build use it); the product path is the
 // HIP library.  It models the gfx950 primitives the body relies on:
-//   v_mfma_f32_32x32x16_{bf16,f16} operand / accumulator lane layouts, ds_read_b64_tr_b16,
+//   v_mfma_f32_32x32x16_{bf16,f16} and v_mfma_f32_16x16x32_{bf16,f16} operand / accumulator lane layouts, ds_read_b64_tr_b16,
 //   RNE fp32->bf16/f16 packing, 8-byte predicated global accesses.
 #include <math.h>
 #include <pthread.h>
@@ -57,6 +57,8 @@ static thread_local WgCtx* g_wg = nullptr;
 static thread_local int g_wave = 0;
 static thread_local Vec<float> g_agpr[128];   // per-wave accumulation registers (DevB: a0..a127)
 static std::atomic<long> g_dma_count{0};      // LDS-DMA instructions executed (tests: the path under test really ran)
+static std::atomic<long> g_gs_count{0};       // runs of a direct-store kernel variant (FwdRoute::gs / BwdRoute::gs), likewise
+static int g_sim_flags = 0;                   // tuning flags (FFC_FLAGS) of the next calls: ffcsim_set_flags
 
 static inline float dt_to_f32(int DT, uint16_t h) { return DT == DT_BF16 ? bf16_to_f32(h) : f16_to_f32(h); }
 static inline uint16_t f32_to_dt(int DT, float f) { return DT == DT_BF16 ? f32_to_bf16(f) : f32_to_f16(f); }
@@ -73,6 +75,8 @@ struct SimB {
   struct U4 { u32 x, y, z, w; };
   struct A16 { f32 v[16]; f32& operator[](int i) { return v[i]; } const f32& operator[](int i) const { return v[i]; } };
   struct W4 { u32 v[4]; u32& operator[](int i) { return v[i]; } const u32& operator[](int i) const { return v[i]; } };
+  struct A4 { f32 v[4]; f32& operator[](int i) { return v[i]; } const f32& operator[](int i) const { return v[i]; } };
+  static A4 a4_zero() { A4 z; for (int i = 0; i < 4; i++) z.v[i] = f32(0.f); return z; }
   template <bool CONJ> static void cmul16(A16& re, A16& im, const A16& tr, const A16& ti) {
     for (int r = 0; r < 16; r++) {
       f32 a = re[r], b = im[r];
@@ -200,6 +204,7 @@ struct SimB {
     for (int i = 0; i < 64; i++) { chk(lds_off + 16 * i, 16); memcpy(L() + lds_off + 16 * i, (const uint8_t*)base + 16 * (int64_t)o16.v[i], 16); }
   }
   static void vm_wait0() {}
+  static void lds_wait0() {}
   static void lds_w32p(const i32& off, const u32& v, const pred& p) {
     for (int i = 0; i < 64; i++) if (p.v[i]) { chk(off.v[i], 4); memcpy(L() + off.v[i], &v.v[i], 4); }
   }
@@ -246,6 +251,7 @@ struct SimB {
     for (int i = 0; i < 64; i++)
       if (p.v[i]) { uint8_t* q = (uint8_t*)base + (int64_t)o8.v[i] * 8; memcpy(q, &v.x.v[i], 4); memcpy(q + 4, &v.y.v[i], 4); }
   }
+  static void g_w64_nt(void* base, const i32& o8, const U2& v, const pred& p) { g_w64(base, o8, v, p); }
   static U4 g_r128(const void* base, const i32& o16) {
     U4 r;
     for (int i = 0; i < 64; i++) {
@@ -290,6 +296,26 @@ struct SimB {
         int i = acc_row(r, l >> 5), j = l & 31;
         float s = 0;
         for (int k = 0; k < 16; k++) s += A[i][k] * Bm[k][j];
+        acc[r].v[l] += s;
+      }
+  }
+  // v_mfma_f32_16x16x32: D[i][j] += sum_k A[i][k] B[k][j];  A lane l: A[l&15][8*(l>>4)+e];  B lane l: B[8*(l>>4)+e][l&15];
+  // D lane l reg r: D[4*(l>>4)+r][l&15]  (CDNA4 ISA, MFMA register layouts of the 16x16x32 16-bit forms).
+  template <int DT>
+  static void mfma16(A4& acc, const W4& a, const W4& b) {
+    float A[16][32], Bm[32][16];
+    for (int l = 0; l < 64; l++)
+      for (int e = 0; e < 8; e++) {
+        uint16_t ha = (uint16_t)(a[e >> 1].v[l] >> (16 * (e & 1)));
+        uint16_t hb = (uint16_t)(b[e >> 1].v[l] >> (16 * (e & 1)));
+        A[l & 15][8 * (l >> 4) + e] = dt_to_f32(DT, ha);
+        Bm[8 * (l >> 4) + e][l & 15] = dt_to_f32(DT, hb);
+      }
+    for (int l = 0; l < 64; l++)
+      for (int r = 0; r < 4; r++) {
+        int i = 4 * (l >> 4) + r, j = l & 15;
+        float s = 0;
+        for (int k = 0; k < 32; k++) s += A[i][k] * Bm[k][j];
         acc[r].v[l] += s;
       }
   }
@@ -352,6 +378,20 @@ static int sim_conv_t(const ConvArgs& a) {
   static_assert(BD::IPASS_BYTES == IPASS_BYTES && GEO::WGW == 8, "ffc_route.h");
   const FwdRoute r = fwd_route<GEO>(a);
   if (r.err) return NO_KERNEL;
+  if (r.gs) {      // conv_kernel<.., GS>: phase C stores the rows (ConvLaunch)
+    if constexpr (!SB::HAS_ADD && GEO::N == 32768) {
+      g_gs_count++;
+      return pick([&](auto sz) -> int {
+        return sim_jobs(a.H, a.nchunk, r.lds, [&](int h, int c) {
+          BD::setup_tables(a.tab, a.t);
+          if (a.kfuse_k || a.kfuse_x) Modes<SB, GEO, DT>::kfft_head(a, h);
+          BD::template conv_job<true, false, decltype(sz)::value, false, true>(a, h, c);
+        });
+      }, r.sz);
+    } else {
+      return NO_KERNEL;
+    }
+  }
   return pick([&](auto mp, auto half, auto sz, auto sp) -> int {
     constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value, SZ = decltype(sz)::value, SP = decltype(sp)::value;
     if constexpr (!fwd_kernel_exists<GEO>(SB::HAS_ADD, MP, HALF, SZ, SP)) {
@@ -406,6 +446,15 @@ static int sim_bwd_t(const DkfArgs& d) {
   const BwdRoute r = bwd_route<GEO>(d, DKF);
   if (r.err) return NO_KERNEL;
   const int H = d.c.H, nchunk = d.c.nchunk, lds = sim_lds<GEO>();
+  if (r.gs) {      // bwd_kernel<.., GS> (BwdLaunchZ)
+    if constexpr (GEO::N == 32768) {
+      g_gs_count++;
+      if (d.zin) return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template bwd<true, false, true, 1, true>(d, h, c, h * nchunk + c); });
+      return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template bwd<true, false, true, 0, true>(d, h, c, h * nchunk + c); });
+    } else {
+      return NO_KERNEL;
+    }
+  }
   return pick([&](auto mp, auto half, auto fastk, auto zm) -> int {
     constexpr bool MP = decltype(mp)::value, HALF = decltype(half)::value, FASTK = decltype(fastk)::value, ZM = decltype(zm)::value;
     if constexpr (!GEO::OUTER) {       // single-tile kernels: one instantiation, saved spectra decided at run time
@@ -448,6 +497,31 @@ template <class GEO, int DT> struct DkRun {
 };
 template <class GEO, int DT> struct UpwGet { static int run(int* out) { *out = GEO::UPW; return 0; } };
 
+// Body::outer_inv_half<false> alone on one unit of fft 32768: e_in [2 planes][32 rows k1][1024 columns] dtype bits (natural order) is laid
+// out in E, the stage runs on the workgroup's 8 waves, e_out [2 planes][16 rows n1][1024 columns] is read back from E
+template <int DT>
+static void sim_outer_inv_half(const HostPlan& p, const uint16_t* e_in, uint16_t* e_out) {
+  using GEO = Geo<32, 32, 32>;
+  using BD = Body<SimB, GEO, DT>;
+  run_wg(8, GEO::LDS_BYTES, [&]() {
+    BD::setup_tables(p.blob.data(), p.tabs);
+    typename BD::Unit un;
+    un.eb = 0; un.wq = g_wave;
+    if (g_wave == 0)
+      for (int pl = 0; pl < 2; pl++)
+        for (int row = 0; row < 32; row++)
+          for (int m = 0; m < 1024; m++)
+            memcpy(SimB::L() + pl * GEO::PLANE + e_off<GEO, int>(row, m), &e_in[(pl * 32 + row) * 1024 + m], 2);
+    SimB::barrier();
+    BD::template outer_inv_half<false>(un);
+    SimB::barrier();
+    if (g_wave == 0)
+      for (int pl = 0; pl < 2; pl++)
+        for (int row = 0; row < 16; row++)
+          for (int m = 0; m < 1024; m++)
+            memcpy(&e_out[(pl * 16 + row) * 1024 + m], SimB::L() + pl * GEO::PLANE + e_off<GEO, int>(row, m), 2);
+  });
+}
 }  // namespace ffc
 
 using namespace ffc;
@@ -484,6 +558,27 @@ int ffcsim_selftest_primitives(const uint32_t* in, uint32_t* out) {
   return 0;
 }
 
+// B::mfma16 alone: a, b [64 lanes][4 dwords] operand registers, d [64 lanes][4] accumulator registers (in: C, out: D)
+int ffcsim_mfma16(int dtype, const uint32_t* a, const uint32_t* b, float* d) {
+  SimB::W4 wa, wb;
+  SimB::A4 acc;
+  for (int l = 0; l < 64; l++)
+    for (int i = 0; i < 4; i++) { wa[i].v[l] = a[l * 4 + i]; wb[i].v[l] = b[l * 4 + i]; acc[i].v[l] = d[l * 4 + i]; }
+  if (dtype == DT_BF16) SimB::mfma16<DT_BF16>(acc, wa, wb);
+  else SimB::mfma16<DT_F16>(acc, wa, wb);
+  for (int l = 0; l < 64; l++)
+    for (int i = 0; i < 4; i++) d[l * 4 + i] = acc[i].v[l];
+  return 0;
+}
+
+int ffcsim_outer_inv_half(int dtype, const uint16_t* e_in, uint16_t* e_out) {
+  HostPlan p;
+  if (!build_plan(32768, dtype, &p)) return -1;
+  if (dtype == DT_BF16) sim_outer_inv_half<DT_BF16>(p, e_in, e_out);
+  else sim_outer_inv_half<DT_F16>(p, e_in, e_out);
+  return 0;
+}
+
 // Plan introspection (also used by tests to build k_f in internal order on the host).
 int ffcsim_plan_info(int N, int dtype, int* nt, double* s_fwd, double* s_k, int32_t* kf_freq /* nt*1024 or null */) {
   HostPlan p;
@@ -501,6 +596,8 @@ void ffcsim_set_sparse(int rows) { g_sparse_rows = rows; }      // next ffcsim_c
 static void* g_z = nullptr; static void* g_yraw = nullptr; static int g_flags = 0;
 void ffcsim_set_z(void* z, void* yraw, int flags) { g_z = z; g_yraw = yraw; g_flags = flags; }
 long ffcsim_dma_count() { return g_dma_count.exchange(0); }
+long ffcsim_gs_count() { return g_gs_count.exchange(0); }
+void ffcsim_set_flags(int flags) { g_sim_flags = flags; }      // ConvArgs::flags of the next forward / backward calls (256: earlier phase C)
 // dk (H, Lk) fp32 written by the NEXT ffcsim_conv_bwd itself (DkfArgs::dk_out, Modes::dk_tail; the caller passes nchunk = 1)
 static float* g_dk_out = nullptr; static int g_dk_lk = 0;
 void ffcsim_set_fused_dk(float* dk, int Lk) { g_dk_out = dk; g_dk_lk = Lk; }
@@ -527,6 +624,7 @@ int ffcsim_conv_fwd(int N, int dtype, const void* u, const void* kf, const void*
   a.nchunk = 1; a.ppc = a.npair; a.conj_kf = conj_kf; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
   a.fast = (L % 8 == 0) && !g_force_slow;
   a.R = p.R;
+  a.flags = g_sim_flags;
   a.sparse = g_sparse_rows;
   if (p.N1 > 1 && p.R == 1) { a.zsave = g_z; a.yraw = g_z ? g_yraw : nullptr; }
   if (p.N1 <= 1) { a.zsave = g_z; a.yraw = g_yraw; }      // single-tile sizes: either one alone too (conv_fwd_impl)
@@ -566,6 +664,7 @@ int ffcsim_conv_fwd_res(int N, int dtype, const void* u, const void* kf, const v
   a.nchunk = 1; a.ppc = a.npair; a.conj_kf = conj_kf; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
   a.fast = (L % 8 == 0) && !((sb_u | sb_pre | sb_post | sb_y | sb_add) & 7) && !g_force_slow;
   a.R = p.R;
+  a.flags = g_sim_flags;
   a.zsave = zsave; a.yraw = y_raw;
   if (!addend) return dispatch<ConvRun>(N, dtype, a);
   return dispatch<ConvResRun>(N, dtype, a);
@@ -706,6 +805,30 @@ int ffcsim_launch_route(int N, int dtype, int B, int H, int L, int nchunk, int p
   return 0;
 }
 
+// Which sink phase C takes (ffc::direct_store_ok through fwd_route / bwd_route): out[0] forward, out[1] fused backward, out[2] dk_f
+// accumulation; 1 = the output rows are stored by phase C itself.  flags as ffcsim_launch_route | 1 << 20: an output gate (forward) / an
+// input gate (backward) | 1 << 21: an addend (forward) / a dpregate output (backward).
+int ffcsim_launch_sink(int N, int dtype, int B, int H, int L, int flags, int* out) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  static char buf[16];
+  DkfArgs d{};
+  ConvArgs& a = d.c;
+  a.B = B; a.H = H; a.L = L; a.npair = (B + 1) / 2; a.nchunk = 1; a.R = p.R; a.flags = flags & 0xffff;
+  a.zsave = (flags & (1 << 16)) ? buf : nullptr; a.yraw = (flags & (1 << 17)) ? buf : nullptr;
+  a.sparse = (flags & (1 << 18)) ? 2 : 0; a.fast = (flags & (1 << 19)) ? 1 : 0;
+  with_geo(N, [&](auto geo) {
+    using GEO = decltype(geo);
+    ConvArgs f = a;
+    f.postgate = (flags & (1 << 20)) ? buf : nullptr; f.addend = (flags & (1 << 21)) ? buf : nullptr;
+    out[0] = fwd_route<GEO>(f).gs;
+    a.pregate = (flags & (1 << 20)) ? buf : nullptr; d.dpre = (flags & (1 << 21)) ? buf : nullptr;
+    out[1] = bwd_route<GEO>(d, false).gs;
+    out[2] = bwd_route<GEO>(d, true).gs;
+  });
+  return 0;
+}
+
 int ffcsim_kernel_fft_c(int N, int dtype, const void* xpair, int H, void* kf, float scale) {
   HostPlan p;
   if (!build_plan(N, dtype, &p)) return -1;
@@ -771,7 +894,8 @@ int ffcsim_conv_bwd(int N, int dtype, const void* dout, const void* u, const voi
   a.fast = (L % 8 == 0) && !g_force_slow;
   a.R = p.R;
   d.dout = dout; d.ws = ws; d.du = du; d.dpre = dpre; d.dpost = (p.N1 > 1 || g_yraw) ? dpost : nullptr;
-  if (p.N1 > 1 && p.R == 1 && g_z) { d.zin = g_z; d.yraw = g_yraw; a.flags = g_flags; a.stream = 1; }
+  a.flags = g_sim_flags;
+  if (p.N1 > 1 && p.R == 1 && g_z) { d.zin = g_z; d.yraw = g_yraw; a.flags = g_flags | g_sim_flags; a.stream = 1; }
   if (p.N1 <= 1) { d.zin = g_z; d.yraw = dpost ? g_yraw : nullptr; }      // (conv_bwd_impl: y_raw with or without the spectra)
   HostPlan pbf;
   // the library's rule for dk out of the backward launch, with fft 8192 asked for as tuning flag 128 does
