@@ -316,16 +316,18 @@ struct Body {
     }
   }
   // table pieces of this thread: loads from a clamped index (always issued, no exec-masked branch), LDS writes under the predicate
+  // wv >= 0: the caller's wave index (a kernel that copies tables a second time, at its end, passes the value it already holds in a
+  // scalar register: asking B::wave() there keeps the work-item id register alive across the whole pair loop)
   static constexpr int TAB_T = GEO::WGW * 64;
   template <int BYTES>
-  static FFC_FN void tab_issue(const uint8_t* src, U4 (&v)[(BYTES / 16 + TAB_T - 1) / TAB_T]) {
-    const i32 tid = B::lane() + B::wave() * 64;
+  static FFC_FN void tab_issue(const uint8_t* src, U4 (&v)[(BYTES / 16 + TAB_T - 1) / TAB_T], int wv = -1) {
+    const i32 tid = B::lane() + (wv >= 0 ? wv : B::wave()) * 64;
 #pragma unroll
     for (int it = 0; it < (BYTES / 16 + TAB_T - 1) / TAB_T; it++) v[it] = B::g_r128(src, B::imin(tid + it * TAB_T, BYTES / 16 - 1));
   }
   template <int BYTES>
-  static FFC_FN void tab_commit(int lds_off, const U4 (&v)[(BYTES / 16 + TAB_T - 1) / TAB_T]) {
-    const i32 tid = B::lane() + B::wave() * 64;
+  static FFC_FN void tab_commit(int lds_off, const U4 (&v)[(BYTES / 16 + TAB_T - 1) / TAB_T], int wv = -1) {
+    const i32 tid = B::lane() + (wv >= 0 ? wv : B::wave()) * 64;
 #pragma unroll
     for (int it = 0; it < (BYTES / 16 + TAB_T - 1) / TAB_T; it++) {
       i32 idx = tid + it * TAB_T;
@@ -335,22 +337,22 @@ struct Body {
   // Round 4: every table's loads are requested first, then written to LDS (copy_tab one table after the other put each load into
   // its own branch followed by s_waitcnt vmcnt(0): 3 .. 6 L2 round trips in a row at the start of every workgroup -- a tenth of the
   // run time of the short-sequence launches).
-  static FFC_FN void setup_tables(const uint8_t* tab, const PlanTabs& t) {
+  static FFC_FN void setup_tables(const uint8_t* tab, const PlanTabs& t, int wv = -1) {
     U4 f1[(6144 / 16 + TAB_T - 1) / TAB_T], f2[(6144 / 16 + TAB_T - 1) / TAB_T], f3[(6144 / 16 + TAB_T - 1) / TAB_T],
        tw[(8192 / 16 + TAB_T - 1) / TAB_T], tw2[(8192 / 16 + TAB_T - 1) / TAB_T], fs[(3072 / 16 + TAB_T - 1) / TAB_T];
-    if constexpr (GEO::OUTER) tab_issue<6144>(tab + t.mat[0], f1);
-    tab_issue<6144>(tab + t.mat[1], f2);
-    tab_issue<8192>(tab + t.twin, tw);
-    if constexpr (GEO::N3 != GEO::N2) tab_issue<6144>(tab + t.mat[2], f3);
-    if constexpr (GEO::TW2_SEP) tab_issue<8192>(tab + t.twin2, tw2);
-    if constexpr (GEO::HAS_SP) tab_issue<3072>(tab + t.mat_sp, fs);
+    if constexpr (GEO::OUTER) tab_issue<6144>(tab + t.mat[0], f1, wv);
+    tab_issue<6144>(tab + t.mat[1], f2, wv);
+    tab_issue<8192>(tab + t.twin, tw, wv);
+    if constexpr (GEO::N3 != GEO::N2) tab_issue<6144>(tab + t.mat[2], f3, wv);
+    if constexpr (GEO::TW2_SEP) tab_issue<8192>(tab + t.twin2, tw2, wv);
+    if constexpr (GEO::HAS_SP) tab_issue<3072>(tab + t.mat_sp, fs, wv);
     B::sched_fence();
-    if constexpr (GEO::OUTER) tab_commit<6144>(GEO::L_F1, f1);
-    tab_commit<6144>(GEO::L_F2, f2);
-    tab_commit<8192>(GEO::L_TW, tw);
-    if constexpr (GEO::N3 != GEO::N2) tab_commit<6144>(GEO::L_F3, f3);
-    if constexpr (GEO::TW2_SEP) tab_commit<8192>(GEO::L_TW2, tw2);
-    if constexpr (GEO::HAS_SP) tab_commit<3072>(GEO::L_FS, fs);
+    if constexpr (GEO::OUTER) tab_commit<6144>(GEO::L_F1, f1, wv);
+    tab_commit<6144>(GEO::L_F2, f2, wv);
+    tab_commit<8192>(GEO::L_TW, tw, wv);
+    if constexpr (GEO::N3 != GEO::N2) tab_commit<6144>(GEO::L_F3, f3, wv);
+    if constexpr (GEO::TW2_SEP) tab_commit<8192>(GEO::L_TW2, tw2, wv);
+    if constexpr (GEO::HAS_SP) tab_commit<3072>(GEO::L_FS, fs, wv);
     B::barrier();
   }
   static FFC_FN void lds_mat(Mat& m, int off) {
@@ -652,6 +654,77 @@ struct Body {
     RowRegsT<NC> X;
     rows_load<NC>(a, h, pq, un, X);
     rows_store<NC>(a, h, pq, un, X);
+  }
+  // ------------------------------------------------------------------ plain input rows, decided at compile time (PL)
+  // The kernels whose host route has already established 16-byte rows with no gate and no side product on the way in
+  // (ffc::plain_rows_ok): the same loads, masks and LDS writes as the fast arm of rows_load / rows_store above and nothing else.  With the
+  // run-time arms in the same kernel (gate product, side product, element-wise loads) every row load and every LDS write sat in flow
+  // blocks of its own, and each merge carried a `s_waitcnt vmcnt(0)`: the top of the pair loop waited for the output stores that phase C
+  // had just issued, and the prefetch behind phase B for the spectrum stores.  Here the burst is straight-line code: NC chunks x 2
+  // planes of unconditional 16-byte loads from clamped positions (chunks beyond L re-read the row's last 16 bytes; rows_store_pl zeroes
+  // them like any tail), the non-temporal choice one wave-uniform branch around the whole burst, as in rows_dma.
+  template <int NC, bool NT>
+  static FFC_FN void rows_load_pl_t(const ConvArgs& a, int h, int pq, Unit un, RowRegsT<NC>& X) {
+    static_assert(GEO::OUTER, "plain-row kernels: sizes with an outer digit");
+    const i32 lane = B::opaque(B::lane());
+#pragma unroll
+    for (int ii = 0; ii < NC; ii++) {
+      i32 idx = lane + ii * 64;
+      i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        const int b = 2 * pq + pl;
+        const bool ok = b < a.B;
+        const uint16_t* base = (const uint16_t*)a.u + row_off(b, ok, a.sbu, h, a.L);
+        const i32 n16 = B::imin(row * GEO::Mi + m, a.L - 8) >> 3;
+        X.v[ii][pl] = NT ? B::g_r128_nt(base, n16) : B::g_r128(base, n16);
+      }
+    }
+  }
+  template <int NC>
+  static FFC_FN void rows_load_pl(const ConvArgs& a, int h, int pq, Unit un, RowRegsT<NC>& X) {
+    if (a.stream) rows_load_pl_t<NC, true>(a, h, pq, un, X);
+    else rows_load_pl_t<NC, false>(a, h, pq, un, X);
+  }
+  // zero what lies beyond L / B, swizzle, write to E
+  template <int NC>
+  static FFC_FN void rows_store_pl(const ConvArgs& a, int pq, Unit un, const RowRegsT<NC>& X) {
+    const i32 lane = B::opaque(B::lane());
+#pragma unroll
+    for (int ii = 0; ii < NC; ii++) {
+      i32 idx = lane + ii * 64;
+      i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+      pred sw;
+      i32 off = pair_off(row, m, &sw) + un.eb;
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        U4 v = X.v[ii][pl];
+        pred ok = ((row * GEO::Mi + m) < a.L) && ((2 * pq + pl) < a.B);
+        v.x = B::sel(ok, v.x, B::uconst(0)); v.y = B::sel(ok, v.y, B::uconst(0));
+        v.z = B::sel(ok, v.z, B::uconst(0)); v.w = B::sel(ok, v.w, B::uconst(0));
+        U4 o;
+        o.x = B::sel(sw, v.z, v.x); o.y = B::sel(sw, v.w, v.y);
+        o.z = B::sel(sw, v.x, v.z); o.w = B::sel(sw, v.y, v.w);
+        B::lds_w128(off + pl * GEO::PLANE, o, B::ptrue());
+      }
+    }
+  }
+  // PL picks the form: one name for the call sites of the pair loops
+  template <int NC, bool PL>
+  static FFC_FN void rows_load_sel(const ConvArgs& a, int h, int pq, Unit un, RowRegsT<NC>& X) {
+    if constexpr (PL) rows_load_pl<NC>(a, h, pq, un, X);
+    else rows_load<NC>(a, h, pq, un, X);
+  }
+  template <int NC, bool PL>
+  static FFC_FN void rows_store_sel(const ConvArgs& a, int h, int pq, Unit un, const RowRegsT<NC>& X) {
+    if constexpr (PL) rows_store_pl<NC>(a, pq, un, X);
+    else rows_store<NC>(a, h, pq, un, X);
+  }
+  template <int NC, bool PL>
+  static FFC_FN void rows_in_sel(const ConvArgs& a, int h, int pq, Unit un) {
+    RowRegsT<NC> X;
+    rows_load_sel<NC, PL>(a, h, pq, un, X);
+    rows_store_sel<NC, PL>(a, h, pq, un, X);
   }
   // ------------------------------------------------------------------ input rows by LDS-DMA (round 4)
   // 32-point outer digit, L <= N/2 (HALF): E rows n1 >= 16 of a wave's column slice are dead from the moment its phase C has
@@ -2353,10 +2426,12 @@ struct Body {
     if constexpr (GEO::NW > 1) B::barrier();
     else B::lds_fence();
   }
-  // GS: phase C stores the output rows itself (outer_inv_half<true>); instantiated for, and launched on, plain rows only
-  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false>
+  // GS: phase C stores the output rows itself (outer_inv_half<true>); instantiated for, and launched on, plain output rows only
+  // PL: the input rows are plain too (ffc::plain_rows_ok): rows_load_pl / rows_store_pl, no gate, side-product or element-wise arm
+  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false>
   static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0) {
     static_assert(!GS || (HALF && !RP && !SP && HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
+    static_assert(!PL || GS, "plain input rows: a form of the direct-store kernels");
     constexpr int NC = HALF ? NCH / 2 : NCH;
     // HALF: the next pair's rows (32 VGPRs) are prefetched behind the last k_f load of phase B, so they
     // arrive during the last tile / phase C / the stores and no earlier in-order vmcnt wait is delayed.
@@ -2377,7 +2452,7 @@ struct Body {
     const int npass = RP ? a.R : 1;
     const int iters = ((p1 - p0 + GEO::UPW - 1) / GEO::UPW) * npass;
     RowRegsT<NC> X;
-    if constexpr (PREFETCH) { if (p0 + u < p1) rows_load<NC>(a, h, p0 + u, un, X); }
+    if constexpr (PREFETCH) { if (p0 + u < p1) rows_load_sel<NC, PL>(a, h, p0 + u, un, X); }
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0, t1 = 0;
 #define FFC_TICK(k) if (PROF) { t1 = B::clock(); acc[k] += t1 - t0; t0 = t1; }
     // Wave priority by progress.  The SIMD issues oldest-first: of its two resident waves (w and w + 4 of the workgroup) the
@@ -2397,15 +2472,15 @@ struct Body {
       const int p = p0 + (RP ? it / npass : it) * GEO::UPW + u;
       const Pass ps = RP ? make_pass(a, it % npass) : Pass();
       const int hk = RP ? h * ps.R + ps.k0 : h;      // k_f row of this (head, pass)
-      const bool act = p < p1;
+      const bool act = (PL && GEO::UPW == 1) || p < p1;      // (one unit owns the workgroup: every iteration has its pair)
       if (PROF) t0 = B::clock();
       FFC_PRIO(1)
       if (act) {
         if constexpr (RP) {
           rows_in_rp<NC>(a, h, p, un, ps);
         } else {
-          if constexpr (!PREFETCH) rows_load<NC>(a, h, p, un, X);
-          rows_store<NC>(a, h, p, un, X);
+          if constexpr (!PREFETCH) rows_load_sel<NC, PL>(a, h, p, un, X);
+          rows_store_sel<NC, PL>(a, h, p, un, X);
         }
         B::lds_fence();
         FFC_TICK(0)
@@ -2472,7 +2547,7 @@ struct Body {
       unit_barrier();
       FFC_TICK(4)
       FFC_PRIO(3)
-      if constexpr (PREFETCH) { if (it + 1 < iters && p + GEO::UPW < p1) rows_load<NC>(a, h, p + GEO::UPW, un, X); }
+      if constexpr (PREFETCH) { if (it + 1 < iters && p + GEO::UPW < p1) rows_load_sel<NC, PL>(a, h, p + GEO::UPW, un, X); }
       if constexpr (GS) {
         if (act) {
           outer_inv_half<true>(un, &a, h, p);
@@ -2509,13 +2584,13 @@ struct Body {
   // ------------------------------------------------------------------ workgroup entry: conv
   // Workgroup handles head h and one chunk of that head's pairs, UPW units at a time.
   // HALF is chosen by the launcher: 32-point outer digit and L <= N/2
-  template <bool HALF = false, bool SZ = false, bool SP = false, bool GS = false>
+  template <bool HALF = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false>
   static FFC_FN void conv(const ConvArgs& a, int h, int chunk) {
     setup_tables(a.tab, a.t);
-    conv_job<HALF, false, SZ, SP, GS>(a, h, chunk);
+    conv_job<HALF, false, SZ, SP, GS, PL>(a, h, chunk);
   }
   // one (head, chunk) job; the tables are already in LDS.  RP: all passes of a multi-pass size
-  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false>
+  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false>
   static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk) {
     const int wv = B::wave();
     Unit un;
@@ -2526,7 +2601,7 @@ struct Body {
     int p1 = p0 + a.ppc;
     if (p1 > a.npair) p1 = a.npair;
     if constexpr (GEO::OUTER) {
-      outer_jobs<HALF, false, RP, SZ, SP, GS>(a, h, p0, p1, u, un);
+      outer_jobs<HALF, false, RP, SZ, SP, GS, PL>(a, h, p0, p1, u, un);
     } else {
       // one tile of G pairs per wave
       const int q0 = p0 / GEO::G, q1 = (p1 + GEO::G - 1) / GEO::G;

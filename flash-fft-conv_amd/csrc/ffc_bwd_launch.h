@@ -15,7 +15,8 @@
 using namespace ffc;
 
 // GS: the du rows are stored by phase C itself (Modes::bwd; fft 32768 at L <= N/2, plain rows: ffc::direct_store_ok)
-template <class GEO, int DT, bool HALF, int ZM, bool GS = false>
+// PL: a GS kernel without the input-side arms (no input gate, no dpost: ffc::plain_rows_ok)
+template <class GEO, int DT, bool HALF, int ZM, bool GS = false, bool PL = false>
 __global__ __launch_bounds__(GEO::WGW * 64, 2) __attribute__((amdgpu_num_vgpr(128))) void bwd_kernel(DkfArgs d) {
   if constexpr (GEO::NW == 1) {
     // one wave per unit (fft 4096): persistent workgroups walk the (head, chunk) jobs (see conv_kernel); the waves
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(GEO::WGW * 64, 2) __attribute__((amdgpu_num_vgpr(12
     int h, chunk;
     if (!map_block(d.c.H, d.c.nchunk, &h, &chunk)) return;
     stagger_start(d.c.flags);
-    Modes<DevBO, GEO, DT>::template bwd<HALF, false, true, ZM, GS>(d, h, chunk, blockIdx.x);
+    Modes<DevBO, GEO, DT>::template bwd<HALF, false, true, ZM, GS, PL>(d, h, chunk, blockIdx.x);
   }
 }
 // single-tile sizes (fft <= 2048): persistent workgroups (two per CU) walk the (head, chunk) jobs, the plan tables are copied
@@ -74,7 +75,9 @@ struct T {
       return ffc_launch(bwd_kernel_small<GEO, DT>, "bwd_kernel", r.grid, T_, r.lds_max, r.lds, st, d);
     } else if (r.gs) {
       if constexpr (GEO::N == 32768)
-        return ffc_launch(bwd_kernel<GEO, DT, true, ZM, true>, "bwd_kernel (direct store)", r.grid, T_, r.lds_max, r.lds, st, d);
+        return pick([&](auto pl) -> int {
+          return ffc_launch(bwd_kernel<GEO, DT, true, ZM, true, decltype(pl)::value>, "bwd_kernel (direct store)", r.grid, T_, r.lds_max, r.lds, st, d);
+        }, r.pl);
       else
         return ffc_fail("internal: the backward route names a kernel that does not exist");
     } else {

@@ -17,9 +17,9 @@ struct T {
     if (r.err) return ffc_fail(r.err);
     if (r.gs) {      // plain rows of fft 32768 at L <= N/2: the kernels whose phase C stores the rows (FAM::kernel_gs)
       if constexpr (!FAM::HAS_ADD && GEO::N == 32768)
-        return pick([&](auto sz) -> int {
-          return ffc_launch(FAM::template kernel_gs<GEO, DT, decltype(sz)::value>(), FAM::what(false, decltype(sz)::value, false, true), r.grid, GEO::WGW * 64, r.lds_max, r.lds, st, a);
-        }, r.sz);
+        return pick([&](auto sz, auto pl) -> int {      // pl: plain input rows too (ffc::plain_rows_ok)
+          return ffc_launch(FAM::template kernel_gs<GEO, DT, decltype(sz)::value, decltype(pl)::value>(), FAM::what(false, decltype(sz)::value, false, true), r.grid, GEO::WGW * 64, r.lds_max, r.lds, st, a);
+        }, r.sz, r.pl);
       else
         return ffc_fail("internal: the forward route names a kernel that does not exist");
     }

@@ -5,7 +5,8 @@ using namespace ffc;
 static constexpr int SMALL_WAVES = 2;     // waves per SIMD the single-tile kernels (no outer digit) are compiled for
 // SZ: the forward that also stores the pairs' spectra for the backward pass (ConvArgs::zsave; fused sizes with an outer digit)
 // GS: phase C stores the output rows itself (Body::outer_inv_half<true>; fft 32768 at L <= N/2, plain rows: ffc::direct_store_ok)
-template <class GEO, int DT, bool HALF, bool SZ = false, bool SP = false, bool GS = false>
+// PL: a GS kernel whose input rows are plain at compile time as well (Body::rows_load_pl; ffc::plain_rows_ok)
+template <class GEO, int DT, bool HALF, bool SZ = false, bool SP = false, bool GS = false, bool PL = false>
 __global__ __launch_bounds__(GEO::WGW * 64, GEO::OUTER ? 2 : SMALL_WAVES) void conv_kernel(ConvArgs a) {
   using BD = Body<DevB, GEO, DT>;
   if constexpr (GEO::OUTER && GEO::NW == 1) {
@@ -36,9 +37,9 @@ __global__ __launch_bounds__(GEO::WGW * 64, GEO::OUTER ? 2 : SMALL_WAVES) void c
       // k -> k_f of this head first (ConvArgs::kfuse_k, one chunk per head): no separate launch for it
       BD::setup_tables(a.tab, a.t);
       if (a.kfuse_k || a.kfuse_x) Modes<DevB, GEO, DT>::kfft_head(a, h);
-      BD::template conv_job<HALF, false, SZ, SP, GS>(a, h, chunk);
+      BD::template conv_job<HALF, false, SZ, SP, GS, PL>(a, h, chunk);
     } else {
-      BD::template conv<HALF, SZ, SP, GS>(a, h, chunk);
+      BD::template conv<HALF, SZ, SP, GS, PL>(a, h, chunk);
     }
   }
 }
@@ -73,8 +74,8 @@ struct ConvKernels {
     if constexpr (MP) return conv_rp_kernel<GEO, DT, HALF, SZ>;
     else return conv_kernel<GEO, DT, HALF, SZ, SP>;
   }
-  template <class GEO, int DT, bool SZ>
-  static constexpr auto kernel_gs() { return conv_kernel<GEO, DT, true, SZ, false, true>; }
+  template <class GEO, int DT, bool SZ, bool PL>
+  static constexpr auto kernel_gs() { return conv_kernel<GEO, DT, true, SZ, false, true, PL>; }
   static const char* what(bool mp, bool sz, bool sp, bool outer) {
     if (mp) return sz && outer ? "conv_rp_kernel (spectrum-saving)" : "conv_rp_kernel";
     if (sz) return outer ? "conv_kernel (spectrum-saving)" : "conv_kernel (spectrum-saving, single tile)";
@@ -242,7 +243,7 @@ extern "C" int ffc_conv_fwd(const ffc_plan* p, const void* u, const void* kf, co
 }
 
 // ---- profiling build (N = 32768, bf16 only): same body with s_memtime phase counters
-template <class GEO, int DT, bool GS = false>
+template <class GEO, int DT, bool GS = false, bool PL = false>
 __global__ __launch_bounds__(GEO::WGW * 64, 2) void conv_prof_kernel(ConvArgs a) {
   int h, chunk;
   if (!map_block(a.H, a.nchunk, &h, &chunk)) return;
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(GEO::WGW * 64, 2) void conv_prof_kernel(ConvArgs a)
   const int p0 = chunk * a.ppc;
   int p1 = p0 + a.ppc;
   if (p1 > a.npair) p1 = a.npair;
-  if constexpr (GS) BD::template outer_jobs<true, true, false, false, false, true>(a, h, p0, p1, u, un, blockIdx.x);      // (phase C stores the rows: no rows_out column)
+  if constexpr (GS) BD::template outer_jobs<true, true, false, false, false, true, PL>(a, h, p0, p1, u, un, blockIdx.x);      // (phase C stores the rows: no rows_out column)
   else if (16 * GEO::Mi >= a.L) BD::template outer_jobs<true, true>(a, h, p0, p1, u, un, blockIdx.x);
   else BD::template outer_jobs<false, true>(a, h, p0, p1, u, un, blockIdx.x);
 }
@@ -277,6 +278,7 @@ extern "C" int ffc_conv_fwd_prof(const ffc_plan* p, const void* u, const void* k
   const FwdRoute r = fwd_route<GEO>(a);
   const int grid = r.grid;
   if (grid_out) *grid_out = grid;
+  if (r.pl) return ffc_launch(conv_prof_kernel<GEO, DT_BF16, true, true>, "conv_prof_kernel", grid, GEO::WGW * 64, GEO::LDS_BYTES, GEO::LDS_BYTES, (hipStream_t)stream, a);
   if (r.gs) return ffc_launch(conv_prof_kernel<GEO, DT_BF16, true>, "conv_prof_kernel", grid, GEO::WGW * 64, GEO::LDS_BYTES, GEO::LDS_BYTES, (hipStream_t)stream, a);
   return ffc_launch(conv_prof_kernel<GEO, DT_BF16>, "conv_prof_kernel", grid, GEO::WGW * 64, GEO::LDS_BYTES, GEO::LDS_BYTES, (hipStream_t)stream, a);
 }

@@ -967,9 +967,13 @@ struct Modes : Body<B, GEO, DT> {
   // each carries only its own half of the pair loop, and a profile names them apart.
   // GS: the last phase C stores the du rows itself (Body::outer_inv_half<true>): single-pass fft 32768 at L <= N/2 without an input
   // gate or dpregate, 16-byte rows (ffc::direct_store_ok); the dpost transform of a gated call keeps rows_out (its rows are multiplied)
-  template <bool HALF = false, bool RP = false, bool SETUP = true, int ZM = -1, bool GS = false>
+  // PL: the input rows are plain as well (ffc::plain_rows_ok: no input gate, no dpost of either kind, 16-byte rows, DMA not switched off):
+  // the dpost transform arm, the gate and side-product arms of the row loads and, on saved spectra, the register row path are not
+  // instantiated -- `dma` is a compile-time constant
+  template <bool HALF = false, bool RP = false, bool SETUP = true, int ZM = -1, bool GS = false, bool PL = false>
   static FFC_FN void bwd(const DkfArgs& d, int h, int chunk, int wg_linear, int k0 = 0, int wv_in = 0) {
     static_assert(!GS || (HALF && !RP && BD::HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
+    static_assert(!PL || (GS && ZM >= 0), "plain input rows: a form of the direct-store kernels");
     const ConvArgs& a = d.c;
     const Pass ps = RP ? make_pass(a.tab, a.t, a.R, k0) : Pass();
     const int hk = RP ? h * a.R + k0 : h;          // k_f row of this (head, pass)
@@ -995,10 +999,10 @@ struct Modes : Body<B, GEO, DT> {
     ConvArgs aq = a;            // dpost = conv(u*pregate, k) * dout
     aq.y = d.dpost; aq.postgate = d.dout; aq.sby = d.sbdpost; aq.sbp = d.sbd;
     // saved forward output (d.yraw): dpost = dout * yraw falls out of the dout row load, no transform for it
-    const bool dpost_tf = d.dpost != nullptr && d.yraw == nullptr;
+    const bool dpost_tf = !PL && d.dpost != nullptr && d.yraw == nullptr;
     // (not in the multi-pass kernels of the fused 32768 size: their 128-VGPR budget has no room for it, build.py check_agpr;
     // the launcher runs the product as a streaming kernel of its own there, ffc_k_bwd.hip mul_rows_kernel)
-    if constexpr (!(RP && GEO::OUTER)) {
+    if constexpr (!(RP && GEO::OUTER) && !PL) {
       if (d.dpost && d.yraw) { ad.aux_in = d.yraw; ad.aux_out = d.dpost; ad.sbai = (int64_t)a.H * a.L; ad.sbao = d.sbdpost; }
     }
     // OUTER geometries: one slab per chunk (the units are reduced inside the workgroup); else one per (chunk, unit).
@@ -1022,7 +1026,8 @@ struct Modes : Body<B, GEO, DT> {
       // HALF kernels with a 32-point outer digit, plain rows (no gate multiply / side product on the way in), 16-byte-aligned
       // tensors; tuning flag 8 (FFC_FLAGS) keeps the register path for A/B runs
       constexpr bool DMA_OK = BD::HAS_DMA && HALF && !RP && ZM != 0;
-      const bool dma = DMA_OK && have_z && a.fast && !ad.pregate && !ad.aux_in && !dpost_tf && !(a.flags & 8);
+      static_assert(!PL || ZM == 0 || DMA_OK, "plain rows on saved spectra: the rows come by LDS-DMA");
+      const bool dma = DMA_OK && (PL || (have_z && a.fast && !ad.pregate && !ad.aux_in && !dpost_tf && !(a.flags & 8)));
       if constexpr (DMA_OK) { if (dma && p0 + u < p1) BD::rows_dma(ad, h, p0 + u, un); }
       // wave priority by progress between two barriers (Body::outer_jobs has the measurements): row loads 1, phase A 0, the
       // tile loops 3 then 1 (2 for the second-dispatched wave of the SIMD), phase C 3, stores 2
@@ -1031,7 +1036,7 @@ struct Modes : Body<B, GEO, DT> {
 #pragma unroll 1
       for (int it = 0; it < iters; it++) {
         const int p = p0 + it * GEO::UPW + u;
-        const bool act = p < p1;
+        const bool act = (PL && GEO::UPW == 1) || p < p1;      // (one unit owns the workgroup: every iteration has its pair)
         FFC_BPRIO(1)
         // saved spectra (d.zin): the pair's first transform is skipped, its spectrum is read from the forward pass's copy
         const void* zp = !have_z ? (const void*)zs
@@ -1075,7 +1080,7 @@ struct Modes : Body<B, GEO, DT> {
             }
             if (!done) {
               if constexpr (RP) BD::template rows_in_rp<NCX>(ad, h, p, un, ps);
-              else BD::template rows_in<NCX>(ad, h, p, un);
+              else BD::template rows_in_sel<NCX, PL>(ad, h, p, un);
               B::lds_fence();
               FFC_BPRIO(0)
               BD::template outer_stage<true, HALF, RP, false, FOLDZ>(a.L, un, a.s_fwd, ps);
@@ -1084,7 +1089,7 @@ struct Modes : Body<B, GEO, DT> {
         } else {
           if (act) {
             if constexpr (RP) BD::template rows_in_rp<NCX>(av, h, p, un, ps);
-            else BD::template rows_in<NCX>(av, h, p, un);
+            else BD::template rows_in_sel<NCX, PL>(av, h, p, un);
             B::lds_fence();
             FFC_BPRIO(0)
             BD::template outer_stage<true, HALF, RP>(a.L, un, a.s_fwd, ps);
@@ -1122,7 +1127,7 @@ struct Modes : Body<B, GEO, DT> {
           }
           if (act) {
             if constexpr (RP) BD::template rows_in_rp<NCX>(ad, h, p, un, ps);
-            else BD::template rows_in<NCX>(ad, h, p, un);
+            else BD::template rows_in_sel<NCX, PL>(ad, h, p, un);
             B::lds_fence();
             FFC_BPRIO(0)
             BD::template outer_stage<true, HALF, RP>(a.L, un, a.s_fwd, ps);
@@ -1175,7 +1180,8 @@ struct Modes : Body<B, GEO, DT> {
           using MB = Modes<B, GEO, DT_BF16>;       // the dk inverse always runs in bf16 operand arithmetic
           if constexpr (DT != DT_BF16) {           // fp16 plan: swap the plan's bf16 tables into LDS first
             B::barrier();
-            MB::BD::setup_tables(d.tab_bf, d.t_bf);
+            if constexpr (PL) MB::BD::setup_tables(d.tab_bf, d.t_bf, wv);      // (no scratch spill of the work-item id: tab_issue)
+            else MB::BD::setup_tables(d.tab_bf, d.t_bf);
           }
           if constexpr (GEO::UPW == 1) MB::dk_tail(d, h, un.wq);
           else MB::dk_tail_multi(d, h, u, un.wq);

@@ -60,6 +60,7 @@ struct FwdRoute {
   int grid, lds_max, lds;      // workgroups, dynamic-LDS limit of the kernel, dynamic LDS of this launch
   const char* err;      // non-null: no kernel for this call
   bool gs;              // GS: phase C stores the output rows itself (Body::outer_inv_half<true>), see direct_store_ok
+  bool pl;              // PL: a GS kernel whose input rows are plain at compile time as well, see plain_rows_ok
 };
 // Where phase C may store its rows straight to global memory: single-pass fft 32768 at L <= N/2, plain output rows -- 16-byte-aligned
 // tensors with L % 8 == 0 (`fast`), and nothing that multiplies, adds to or copies the rows on their way out (`plain`).  Tuning flag 256
@@ -68,6 +69,11 @@ template <class GEO>
 inline bool direct_store_ok(bool half, bool multi_pass, int fast, bool plain, int flags) {
   return GEO::N == 32768 && half && !multi_pass && fast && plain && !(flags & 256);
 }
+// Where the rows also come IN plain: a direct-store call (so 16-byte rows: `fast`) with nothing that multiplies the input rows or takes a
+// side product from them (`plain_in`).  Those calls run the PL form of the GS kernels, which has no gate, side-product or element-wise arm
+// in its pair loop (Body::rows_load_pl; the backward on saved spectra takes its rows by LDS-DMA unconditionally, so tuning flag 8 is part
+// of its `plain_in`).  Tuning flag 512 keeps the GS kernels with the run-time arms.
+inline bool plain_rows_ok(bool gs, bool plain_in, int flags) { return gs && plain_in && !(flags & 512); }
 template <class GEO>
 inline FwdRoute fwd_route(const ConvArgs& a) {
   FwdRoute r{};
@@ -99,6 +105,7 @@ inline FwdRoute fwd_route(const ConvArgs& a) {
   // y_raw without the spectra: the single-tile sizes only
   r.sz = a.zsave || (!GEO::OUTER && a.yraw);
   r.gs = direct_store_ok<GEO>(r.half, false, a.fast, !a.postgate && !a.addend && !a.yraw, a.flags);
+  r.pl = plain_rows_ok(r.gs, !a.pregate && !a.aux_in, a.flags);
   return r;
 }
 // the forward instantiations that exist (add: the family with an addend in the output epilogue has no frequency-sparse form)
@@ -118,6 +125,7 @@ struct BwdRoute {
   int grid, lds_max, lds;
   const char* err;
   bool gs;              // bwd_kernel only: the du rows from phase C itself (no input gate, no dpregate), see direct_store_ok
+  bool pl;              // bwd_kernel only: a GS kernel whose dout (and u) rows come in plain as well, see plain_rows_ok
 };
 template <class GEO>
 inline BwdRoute bwd_route(const DkfArgs& d, bool dkf) {
@@ -136,6 +144,7 @@ inline BwdRoute bwd_route(const DkfArgs& d, bool dkf) {
     if (GEO::NW == 1 && c.persist > 0 && r.grid > c.persist) r.grid = c.persist;      // persistent: one workgroup per CU (fft 4096)
     r.half = (GEO::N1 / 2) * GEO::Mi >= c.L;
     r.gs = !dkf && direct_store_ok<GEO>(r.half, false, c.fast, !c.pregate && !d.dpre, c.flags);
+    r.pl = plain_rows_ok(r.gs, !c.postgate && !d.dpost && !d.yraw && !(c.flags & 8), c.flags);
     return r;
   }
   r.small = true;

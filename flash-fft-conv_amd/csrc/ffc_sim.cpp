@@ -58,6 +58,7 @@ static thread_local int g_wave = 0;
 static thread_local Vec<float> g_agpr[128];   // per-wave accumulation registers (DevB: a0..a127)
 static std::atomic<long> g_dma_count{0};      // LDS-DMA instructions executed (tests: the path under test really ran)
 static std::atomic<long> g_gs_count{0};       // runs of a direct-store kernel variant (FwdRoute::gs / BwdRoute::gs), likewise
+static std::atomic<long> g_pl_count{0};       // ... and of their plain-input forms (FwdRoute::pl / BwdRoute::pl)
 static int g_sim_flags = 0;                   // tuning flags (FFC_FLAGS) of the next calls: ffcsim_set_flags
 
 static inline float dt_to_f32(int DT, uint16_t h) { return DT == DT_BF16 ? bf16_to_f32(h) : f16_to_f32(h); }
@@ -381,13 +382,14 @@ static int sim_conv_t(const ConvArgs& a) {
   if (r.gs) {      // conv_kernel<.., GS>: phase C stores the rows (ConvLaunch)
     if constexpr (!SB::HAS_ADD && GEO::N == 32768) {
       g_gs_count++;
-      return pick([&](auto sz) -> int {
+      if (r.pl) g_pl_count++;
+      return pick([&](auto sz, auto pl) -> int {
         return sim_jobs(a.H, a.nchunk, r.lds, [&](int h, int c) {
           BD::setup_tables(a.tab, a.t);
           if (a.kfuse_k || a.kfuse_x) Modes<SB, GEO, DT>::kfft_head(a, h);
-          BD::template conv_job<true, false, decltype(sz)::value, false, true>(a, h, c);
+          BD::template conv_job<true, false, decltype(sz)::value, false, true, decltype(pl)::value>(a, h, c);
         });
-      }, r.sz);
+      }, r.sz, r.pl);
     } else {
       return NO_KERNEL;
     }
@@ -449,8 +451,12 @@ static int sim_bwd_t(const DkfArgs& d) {
   if (r.gs) {      // bwd_kernel<.., GS> (BwdLaunchZ)
     if constexpr (GEO::N == 32768) {
       g_gs_count++;
-      if (d.zin) return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template bwd<true, false, true, 1, true>(d, h, c, h * nchunk + c); });
-      return sim_jobs(H, nchunk, lds, [&](int h, int c) { MO::template bwd<true, false, true, 0, true>(d, h, c, h * nchunk + c); });
+      if (r.pl) g_pl_count++;
+      return pick([&](auto zm, auto pl) -> int {
+        return sim_jobs(H, nchunk, lds, [&](int h, int c) {
+          MO::template bwd<true, false, true, decltype(zm)::value ? 1 : 0, true, decltype(pl)::value>(d, h, c, h * nchunk + c);
+        });
+      }, d.zin != nullptr, r.pl);
     } else {
       return NO_KERNEL;
     }
@@ -597,6 +603,7 @@ static void* g_z = nullptr; static void* g_yraw = nullptr; static int g_flags = 
 void ffcsim_set_z(void* z, void* yraw, int flags) { g_z = z; g_yraw = yraw; g_flags = flags; }
 long ffcsim_dma_count() { return g_dma_count.exchange(0); }
 long ffcsim_gs_count() { return g_gs_count.exchange(0); }
+long ffcsim_pl_count() { return g_pl_count.exchange(0); }
 void ffcsim_set_flags(int flags) { g_sim_flags = flags; }      // ConvArgs::flags of the next forward / backward calls (256: earlier phase C)
 // dk (H, Lk) fp32 written by the NEXT ffcsim_conv_bwd itself (DkfArgs::dk_out, Modes::dk_tail; the caller passes nchunk = 1)
 static float* g_dk_out = nullptr; static int g_dk_lk = 0;
@@ -825,6 +832,32 @@ int ffcsim_launch_sink(int N, int dtype, int B, int H, int L, int flags, int* ou
     a.pregate = (flags & (1 << 20)) ? buf : nullptr; d.dpre = (flags & (1 << 21)) ? buf : nullptr;
     out[1] = bwd_route<GEO>(d, false).gs;
     out[2] = bwd_route<GEO>(d, true).gs;
+  });
+  return 0;
+}
+
+// Which direct-store calls also take their input rows plain (ffc::plain_rows_ok through fwd_route / bwd_route): out[0] forward, out[1] fused
+// backward.  flags as ffcsim_launch_route | 1 << 20: an input gate | 1 << 21: the forward's / backward's dpost side product (aux_in / y_raw)
+// | 1 << 22: a dpost output without y_raw (backward).
+int ffcsim_launch_plain(int N, int dtype, int B, int H, int L, int flags, int* out) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  static char buf[16];
+  DkfArgs d{};
+  ConvArgs& a = d.c;
+  a.B = B; a.H = H; a.L = L; a.npair = (B + 1) / 2; a.nchunk = 1; a.R = p.R; a.flags = flags & 0xffff;
+  a.zsave = (flags & (1 << 16)) ? buf : nullptr;
+  a.fast = (flags & (1 << 19)) ? 1 : 0;
+  with_geo(N, [&](auto geo) {
+    using GEO = decltype(geo);
+    ConvArgs f = a;
+    f.pregate = (flags & (1 << 20)) ? buf : nullptr; f.aux_in = (flags & (1 << 21)) ? buf : nullptr;
+    out[0] = fwd_route<GEO>(f).pl;
+    a.postgate = (flags & (1 << 20)) ? buf : nullptr;
+    d.zin = a.zsave; a.zsave = nullptr;
+    if (flags & (3 << 21)) d.dpost = buf;
+    d.yraw = (flags & (1 << 21)) ? buf : nullptr;
+    out[1] = bwd_route<GEO>(d, false).pl;
   });
   return 0;
 }
