@@ -762,8 +762,15 @@ struct Body {
     }
   }
   // wait for the wave's own copies (the reads that follow are its own: no barrier needed), zero what lies beyond L / B
+  // BEHIND: vector-memory instructions the wave has issued since the end of the rows_dma burst, on every path.  The counter retires in
+  // order, so once at most BEHIND operations are outstanding the copies have landed, and what was queued behind them (the du stores
+  // of phase C's second half) is not waited for.  0: nothing is known to be behind the copies (the prologue of a pair loop): full wait.
+  static constexpr int DMA_COPIES = 2 * (GEO::N1 / 2);      // instructions of one rows_dma burst
+  template <int BEHIND = 0>
   static FFC_FN void rows_dma_finish(const ConvArgs& a, int pq, Unit un) {
-    B::vm_wait0();
+    static_assert(BEHIND >= 0 && BEHIND + DMA_COPIES <= 63, "vmcnt is a 6-bit counter: the copies and what follows them must fit");
+    if constexpr (BEHIND == 0) B::vm_wait0();
+    else B::template vm_wait<BEHIND>();
     const i32 lane = B::opaque(B::lane());
 #pragma unroll
     for (int pl = 0; pl < 2; pl++) {
@@ -1517,10 +1524,12 @@ struct Body {
   //               launched for plain rows only: 16-byte-aligned tensors, L % 8 == 0, no output gate / addend / second copy (ffc_route.h).
   // The K = 32 sum is formed in one instruction, so the last bits may differ from the two-K-step forms; tuning flag 256 keeps those.
   static constexpr bool HALF_C = GEO::N1 == 32 && GEO::N2 == 32 && GEO::N3 == 32;
+  static constexpr int HALF_C_ROWS = 4;                      // output rows per lane: the accumulator registers of one 16x16x32 MFMA
+  static constexpr int HALF_C_STORES = 2 * HALF_C_ROWS;      // GS: store instructions of one 64-column half, both planes
   using A4 = typename B::A4;
   // mid(): called once the half's LDS reads have returned (its first tile's MFMAs are issued), ahead of the other tiles and the stores
   struct NoMid { FFC_FN void operator()() const {} };
-  template <bool GS, class MID>
+  template <bool GS, bool UN, class MID>
   static FFC_FN void outer_inv_half_cols(int hc, Unit un, const W4& Cr, const W4& Ci, const W4& Cn, const ConvArgs* a, int h, int pq, MID mid) {
     const i32 lane = B::opaque(B::lane());
     const i32 c = lane & 15, g = lane >> 4;
@@ -1550,9 +1559,9 @@ struct Body {
       B::template mfma16<DT>(im[t], Cr, di);
       if (t == 0) mid();
     }
-    U2 wr[4], wi[4];
+    U2 wr[HALF_C_ROWS], wi[HALF_C_ROWS];
 #pragma unroll
-    for (int r = 0; r < 4; r++) {
+    for (int r = 0; r < HALF_C_ROWS; r++) {
       wr[r].x = B::template pack<DT>(re[0][r], re[1][r]); wr[r].y = B::template pack<DT>(re[2][r], re[3][r]);
       wi[r].x = B::template pack<DT>(im[0][r], im[1][r]); wi[r].y = B::template pack<DT>(im[2][r], im[3][r]);
     }
@@ -1570,23 +1579,40 @@ struct Body {
         const int b = 2 * pq + pl;
         const bool ok = b < a->B;
         uint16_t* base = (uint16_t*)a->y + row_off(b, ok, a->sby, h, a->L);
+        if constexpr (UN) {
+          // Range-checked stores (B::row_w64): the row's length in bytes is the buffer's size, 0 for the missing row of an odd batch, and
+          // the hardware drops the lanes beyond it.  No predicate, no branch and ONE arm, so that the wait-count pass can count past
+          // them: the rotated pair loop (outer_jobs, ROT) writes the next pair's rows to E right behind these 16 stores, and its waits
+          // for the row loads must not drain them; the backward's (Modes::bwd, ROT) counts HALF_C_STORES of them behind the row copies, which
+          // holds only if every one is issued.  A predicated store is compiled into a block behind a skip-if-no-lane-is-active
+          // branch of its own (on the path where all are skipped nothing stands behind the loads), and with the streaming choice as two
+          // arms around each group of stores the pass loses the count as well (profiles/pair_loop_waits_ab.txt): vmcnt(7) .. (0) either
+          // way, which drains all 16 stores at every pair.  So the output rows of these kernels are always written with the streaming
+          // policy (the launcher's default for them; FFC_STREAM=0 still switches their row loads).
+          const int nb = ok ? a->L * 2 : 0;
+#pragma unroll
+          for (int r = 0; r < HALF_C_ROWS; r++) B::template row_w64<true>(base, nb, (n + r * GEO::Mi) * 2, pl ? wi[r] : wr[r]);
+          continue;
+        }
         // (one branch for the four stores of a plane, not one per instruction)
         if (a->stream) {
 #pragma unroll
-          for (int r = 0; r < 4; r++) B::g_w64_nt(base, (n + r * GEO::Mi) >> 2, pl ? wi[r] : wr[r], ((n + r * GEO::Mi) < a->L) && ok);
+          for (int r = 0; r < HALF_C_ROWS; r++) B::g_w64_nt(base, (n + r * GEO::Mi) >> 2, pl ? wi[r] : wr[r], ((n + r * GEO::Mi) < a->L) && ok);
         } else {
 #pragma unroll
-          for (int r = 0; r < 4; r++) B::g_w64(base, (n + r * GEO::Mi) >> 2, pl ? wi[r] : wr[r], ((n + r * GEO::Mi) < a->L) && ok);
+          for (int r = 0; r < HALF_C_ROWS; r++) B::g_w64(base, (n + r * GEO::Mi) >> 2, pl ? wi[r] : wr[r], ((n + r * GEO::Mi) < a->L) && ok);
         }
       }
     }
   }
   // last(): called when the stage's last LDS read has returned, under the second half's remaining MFMAs and its stores (the backward on
   // saved spectra requests the next pair's rows there: E rows 16.. of the wave's slice are dead from that point on)
-  template <bool GS>
-  static FFC_FN void outer_inv_half(Unit un, const ConvArgs* a = nullptr, int h = 0, int pq = 0) { outer_inv_half<GS>(un, a, h, pq, NoMid()); }
-  template <bool GS, class LAST>
+  // UN: the direct store is issued unconditionally, range-checked by the hardware (the plain-row kernels with the rotated pair loops)
+  template <bool GS, bool UN = false>
+  static FFC_FN void outer_inv_half(Unit un, const ConvArgs* a = nullptr, int h = 0, int pq = 0) { outer_inv_half<GS, UN>(un, a, h, pq, NoMid()); }
+  template <bool GS, bool UN, class LAST>
   static FFC_FN void outer_inv_half(Unit un, const ConvArgs* a, int h, int pq, LAST last) {
+    static_assert(!UN || GS, "unconditional stores: a form of the direct store");
     static_assert(HALF_C && GEO::S1 == 1 && GEO::NW == 8, "half-height phase C: fft 32768");
     static_assert(!GS || !B::HAS_ADD, "the direct store has no addend");
     const i32 lane = B::opaque(B::lane());
@@ -1599,10 +1625,10 @@ struct Body {
     if constexpr (B::LEAN_OUTER) {
 #pragma unroll 1
       for (int hc = 0; hc < 2; hc++)      // (a runtime loop bounds the live ranges)
-        outer_inv_half_cols<GS>(hc, un, Cr, Ci, Cn, a, h, pq, [&]() { if (hc == 1) last(); });
+        outer_inv_half_cols<GS, UN>(hc, un, Cr, Ci, Cn, a, h, pq, [&]() { if (hc == 1) last(); });
     } else {
-      outer_inv_half_cols<GS>(0, un, Cr, Ci, Cn, a, h, pq, NoMid());
-      outer_inv_half_cols<GS>(1, un, Cr, Ci, Cn, a, h, pq, last);
+      outer_inv_half_cols<GS, UN>(0, un, Cr, Ci, Cn, a, h, pq, NoMid());
+      outer_inv_half_cols<GS, UN>(1, un, Cr, Ci, Cn, a, h, pq, last);
     }
   }
 
@@ -2451,6 +2477,13 @@ struct Body {
     // the read-modify-write of the output rows find them in L2
     const int npass = RP ? a.R : 1;
     const int iters = ((p1 - p0 + GEO::UPW - 1) / GEO::UPW) * npass;
+    // ROT: the plain-input kernels run the pair loop rotated -- the first pair's rows are written to E ahead of the loop and every
+    // iteration ends with the LDS writes of the NEXT pair's rows, straight-line behind phase C.  At the top of the loop the wait in
+    // front of those writes had two predecessors, the entry edge (the prologue's loads, nothing behind them) and the back edge (the same
+    // loads with phase C's 16 output stores behind them); the wait-count pass keeps the smaller count of the two, so every pair waited
+    // for 9 of the 16 stores it had just issued.  Behind phase C every path to the writes has passed the stores.
+    constexpr bool ROT = PL && PREFETCH;
+    static_assert(!ROT || GEO::UPW == 1, "rotated pair loop: one unit owns the workgroup, every iteration has its pair");
     RowRegsT<NC> X;
     if constexpr (PREFETCH) { if (p0 + u < p1) rows_load_sel<NC, PL>(a, h, p0 + u, un, X); }
     unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t0 = 0, t1 = 0;
@@ -2467,6 +2500,14 @@ struct Body {
     // (fft 4096, one wave per unit and no barriers between the waves: +3 % with priorities, so only where waves share a unit;
     // same-box A/B: forward -2.1 % at fft 32768, -1.2 % at 16384, -2 % at 8192)
 #define FFC_PRIO(x) if constexpr (GEO::NW > 1) B::template setprio<x>();
+    if constexpr (ROT) {
+      if (p0 + u < p1) {
+        if (PROF) t0 = B::clock();
+        FFC_PRIO(1)
+        rows_store_pl<NC>(a, p0 + u, un, X);
+        FFC_TICK(0)
+      }
+    }
 #pragma unroll 1
     for (int it = 0; it < iters; it++) {
       const int p = p0 + (RP ? it / npass : it) * GEO::UPW + u;
@@ -2474,15 +2515,15 @@ struct Body {
       const int hk = RP ? h * ps.R + ps.k0 : h;      // k_f row of this (head, pass)
       const bool act = (PL && GEO::UPW == 1) || p < p1;      // (one unit owns the workgroup: every iteration has its pair)
       if (PROF) t0 = B::clock();
-      FFC_PRIO(1)
+      if constexpr (!ROT) { FFC_PRIO(1) }
       if (act) {
         if constexpr (RP) {
           rows_in_rp<NC>(a, h, p, un, ps);
-        } else {
+        } else if constexpr (!ROT) {
           if constexpr (!PREFETCH) rows_load_sel<NC, PL>(a, h, p, un, X);
           rows_store_sel<NC, PL>(a, h, p, un, X);
         }
-        B::lds_fence();
+        B::lds_fence();      // (ROT: the pair's rows were written at the bottom of the previous iteration, or in the prologue)
         FFC_TICK(0)
         FFC_PRIO(0)
         outer_stage<true, HALF, RP, false, FOLDF>(a.L, un, a.s_fwd, ps);
@@ -2550,8 +2591,17 @@ struct Body {
       if constexpr (PREFETCH) { if (it + 1 < iters && p + GEO::UPW < p1) rows_load_sel<NC, PL>(a, h, p + GEO::UPW, un, X); }
       if constexpr (GS) {
         if (act) {
-          outer_inv_half<true>(un, &a, h, p);
+          outer_inv_half<true, ROT>(un, &a, h, p);
           FFC_TICK(5)
+        }
+        if constexpr (ROT) {
+          // rows 0..15 of the wave's own column slice: phase C's reads of them have returned (its MFMAs consumed them), and LDS
+          // operations of one wave retire in order
+          if (it + 1 < iters && p + GEO::UPW < p1) {
+            FFC_PRIO(1)
+            rows_store_pl<NC>(a, p + GEO::UPW, un, X);
+            FFC_TICK(0)
+          }
         }
       } else if (act) {
         outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);

@@ -150,6 +150,12 @@ struct DevB {
     else __builtin_amdgcn_global_load_lds(g, l, 16, 0, 0);
   }
   static FFC_FN void vm_wait0() { __builtin_amdgcn_s_waitcnt(0x0F70); }      // s_waitcnt vmcnt(0)
+  // s_waitcnt vmcnt(N): at most N of the wave's vector-memory operations are still outstanding (they retire in order, loads, LDS-DMA
+  // copies and stores alike).  gfx9 encoding: vmcnt = simm16[15:14] : simm16[3:0], expcnt and lgkmcnt left at "no wait"
+  template <int N> static FFC_FN void vm_wait() {
+    static_assert(N >= 0 && N <= 63, "vmcnt is a 6-bit counter");
+    __builtin_amdgcn_s_waitcnt(0x0F70 | (N & 15) | ((N >> 4) << 14));
+  }
   // s_waitcnt lgkmcnt(0): the wave's LDS reads have returned; the scheduling fence keeps what follows behind it
   static FFC_FN void lds_wait0() { __builtin_amdgcn_s_waitcnt(0xC07F); __builtin_amdgcn_sched_barrier(0); }
   static FFC_FN void lds_w32p(i32 off, u32 v, pred p) { if (p) *(uint32_t*)(ffc_smem + off) = v; }
@@ -200,6 +206,15 @@ struct DevB {
   }
   static FFC_FN void g_w64_nt(void* base, i32 o8, U2 v, pred p) {
     if (p) { u32x2v t = {v.x, v.y}; __builtin_nontemporal_store(t, ((u32x2v*)base) + o8); }
+  }
+  // Range-checked row store (buffer_store_dwordx2): the lane's 8 bytes at byte offset `off` of the row that starts at `row` (wave-uniform)
+  // and holds `nbytes` bytes.  The hardware drops every lane with off >= nbytes, so the instruction needs no predicate and no branch:
+  // it is issued, and counted by vmcnt, whatever the lanes do.  Descriptor: base, stride 0 (raw), size in bytes, 32-bit data format.
+  template <bool NT>
+  static FFC_FN void row_w64(void* row, int nbytes, i32 off, U2 v) {
+    __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(row, 0, nbytes, 0x00020000);
+    u32x2v t = {v.x, v.y};
+    __builtin_amdgcn_raw_buffer_store_b64(t, r, off, 0, NT ? 2 : 0);      // (2: the nt bit of the cache policy, as __builtin_nontemporal_store sets it)
   }
   static FFC_FN U4 g_r128(const void* base, i32 o16) {
     uint4 v = ((const uint4*)base)[o16];

@@ -1029,15 +1029,30 @@ struct Modes : Body<B, GEO, DT> {
       static_assert(!PL || ZM == 0 || DMA_OK, "plain rows on saved spectra: the rows come by LDS-DMA");
       const bool dma = DMA_OK && (PL || (have_z && a.fast && !ad.pregate && !ad.aux_in && !dpost_tf && !(a.flags & 8)));
       if constexpr (DMA_OK) { if (dma && p0 + u < p1) BD::rows_dma(ad, h, p0 + u, un); }
+      // ROT: the plain-row kernel on saved spectra runs the pair loop rotated -- the "finish" of a pair's row copies (the wait, the zeroing
+      // of what lies beyond L / B, the fence) stands at the bottom of the previous iteration, behind phase C.  The copies are requested in
+      // the middle of phase C (`mid` below) and the du stores of its second half are queued behind them, HALF_C_STORES instructions on
+      // every path (range-checked stores, outer_inv_half<.., UN>): the wait counts past exactly those (Body::rows_dma_finish<BEHIND>).  The
+      // first pair's copies have nothing behind them: the prologue waits for everything.  (As compiled today the du stores are still
+      // drained: the compiler tracks the copies as pending LDS writes and adds a vmcnt(0) of its own ahead of phase A's first LDS read,
+      // because the path "copies requested, finish skipped" reaches the loop header -- DESIGN.md section 4.1, profiles/pair_loop_waits_ab.txt.)
+      constexpr bool ROT = PL && ZM == 1;
+      static_assert(!ROT || (DMA_OK && GEO::UPW == 1), "rotated pair loop: rows by LDS-DMA, one unit owns the workgroup");
       // wave priority by progress between two barriers (Body::outer_jobs has the measurements): row loads 1, phase A 0, the
       // tile loops 3 then 1 (2 for the second-dispatched wave of the SIMD), phase C 3, stores 2
       const bool second = wv >= 4;
 #define FFC_BPRIO(x) if constexpr (GEO::NW > 1) B::template setprio<x>();
+      if constexpr (ROT) {
+        if (p0 + u < p1) {
+          FFC_BPRIO(1)
+          BD::rows_dma_finish(ad, p0 + u, un);
+        }
+      }
 #pragma unroll 1
       for (int it = 0; it < iters; it++) {
         const int p = p0 + it * GEO::UPW + u;
         const bool act = (PL && GEO::UPW == 1) || p < p1;      // (one unit owns the workgroup: every iteration has its pair)
-        FFC_BPRIO(1)
+        if constexpr (!ROT) { FFC_BPRIO(1) }
         // saved spectra (d.zin): the pair's first transform is skipped, its spectrum is read from the forward pass's copy
         const void* zp = !have_z ? (const void*)zs
                          : RP ? (const void*)BD::z_slot_rp(const_cast<void*>(d.zin), h, a.npair, act ? p : p0, a.R, k0)
@@ -1072,7 +1087,7 @@ struct Modes : Body<B, GEO, DT> {
             bool done = false;
             if constexpr (DMA_OK) {
               if (dma) {      // the rows were requested behind the previous pair's phase C (or in the prologue)
-                BD::rows_dma_finish(ad, p, un);
+                if constexpr (!ROT) BD::rows_dma_finish(ad, p, un);      // (ROT: finished at the bottom of the previous iteration)
                 FFC_BPRIO(0)
                 BD::template outer_stage<true, HALF, RP, true, FOLDZ>(a.L, un, a.s_fwd, ps);
                 done = true;
@@ -1151,11 +1166,18 @@ struct Modes : Body<B, GEO, DT> {
             // the next pair's dout rows into E rows 16.. of the wave's slice, requested as soon as phase C's last LDS read has returned
             // (lds_wait0: the copies go through the vector-memory path, which is not ordered behind pending LDS reads): they are in
             // flight under the second half's MFMAs and the du stores.  Phase C writes nothing to LDS here
-            BD::template outer_inv_half<true>(un, &ao, h, p, [&]() {
+            BD::template outer_inv_half<true, ROT>(un, &ao, h, p, [&]() {
               if constexpr (DMA_OK) {
                 if (dma && p + GEO::UPW < p1) { B::lds_wait0(); BD::rows_dma(ad, h, p + GEO::UPW, un); }
               }
             });
+          }
+          if constexpr (ROT) {
+            // behind the copies the wave has issued the du stores of phase C's second half and nothing else
+            if (p + GEO::UPW < p1) {
+              FFC_BPRIO(1)
+              BD::template rows_dma_finish<BD::HALF_C_STORES>(ad, p + GEO::UPW, un);
+            }
           }
         } else if (act) {
           BD::template outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);

@@ -205,6 +205,7 @@ struct SimB {
     for (int i = 0; i < 64; i++) { chk(lds_off + 16 * i, 16); memcpy(L() + lds_off + 16 * i, (const uint8_t*)base + 16 * (int64_t)o16.v[i], 16); }
   }
   static void vm_wait0() {}
+  template <int N> static void vm_wait() {}
   static void lds_wait0() {}
   static void lds_w32p(const i32& off, const u32& v, const pred& p) {
     for (int i = 0; i < 64; i++) if (p.v[i]) { chk(off.v[i], 4); memcpy(L() + off.v[i], &v.v[i], 4); }
@@ -239,6 +240,12 @@ struct SimB {
   }
   static void g_w32(void* base, const i32& e, const u32& v, const pred& p) {
     for (int i = 0; i < 64; i++) if (p.v[i]) memcpy((uint8_t*)base + (int64_t)e.v[i] * 4, &v.v[i], 4);
+  }
+  // the hardware's range check of a raw buffer: lanes at or beyond the row's size in bytes are dropped
+  template <bool NT>
+  static void row_w64(void* row, int nbytes, const i32& off, const U2& v) {
+    for (int i = 0; i < 64; i++)
+      if ((uint32_t)off.v[i] < (uint32_t)nbytes) { uint8_t* q = (uint8_t*)row + off.v[i]; memcpy(q, &v.x.v[i], 4); memcpy(q + 4, &v.y.v[i], 4); }
   }
   static U2 g_r64(const void* base, const i32& o8, const pred& p) {
     U2 r;
