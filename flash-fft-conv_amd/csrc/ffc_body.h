@@ -1203,6 +1203,23 @@ struct Body {
   // HALF (L <= N/2): E rows n1 >= N1/2 carry no input and their outputs lie beyond L.  c = tile-local row constant
   // (bit 2 clear; the lane adds 4*hi): the row is dead iff (c mod N1) >= N1/2.
   static constexpr bool row_dead(int c) { return (c % GEO::N1) >= GEO::N1 / 2; }
+  // tile-local row R = 4*hi + c (c = acc_row(r, 0) or a K-slot row, a compile-time constant with bit 2 clear) -> column set
+  // s1 = c / N1 and E row rw = c % N1 + 4*hi: the byte offset of E row c % N1 (the column base carries 4*hi)
+  static constexpr int row_byte(int c) { return (c % GEO::N1) * (GEO::Mi * 2); }
+  // multi-pass sizes: the circle the twiddle phases live on (N R points) as chain8p / twiddle16 take it
+  static FFC_FN int rp_nmask(const Pass& ps) { return GEO::N * ps.R - 1; }
+  static FFC_FN float rp_inv_n(const Pass& ps) { return 1.0f / (float)(GEO::N * ps.R); }
+  // s_fwd * W_N^{m*k1} behind the forward outer DFT: registers <-> rows k1 = 4*hi + {0..3} + 8*{0..3} (mod N1), lane / tile <-> column m.
+  // The chain of accumulator half `half` (registers 0-7 / 8-15, rows +16) of column tile `tile`; the caller owns tr / ti and applies
+  // them (apply8).  outer_stage_pair / _quad still write the block out (profiles/body_dedup_isa.txt).
+  template <bool RP>
+  static FFC_FN void outer_fwd_chain(int half, i32 j, i32 hi, int w, int tile, float s_fwd, const Pass& ps, F2 (&tr)[4], F2 (&ti)[4]) {
+    const int s1 = (16 * half) / GEO::N1;     // second half: next column set when N1 == 16
+    i32 m = j * 4 + (s1 * 128 + w * 128 * GEO::S1 + tile);
+    i32 k0 = hi * 4 + ((16 * half) % GEO::N1);
+    if constexpr (RP) chain8p(m * (k0 * ps.R + ps.k0), m * ps.R, -1.0f, s_fwd, tr, ti, rp_nmask(ps), rp_inv_n(ps));
+    else chain8p(m * k0, m, -1.0f, s_fwd, tr, ti);
+  }
 
   // The wave owns columns [wq*128*S1, +128*S1) of every E row: 4 tiles t, lane j <-> column
   // s1*128 + 4j + t.  FWD: rows are n1 (real pair x), result rows k1 with the W_N^{m k1} twiddle.
@@ -1210,13 +1227,10 @@ struct Body {
   // HALF: input rows n1 >= 16 are all zero (L <= 16*Mi, 32-point outer digit) -> one K-step.
   template <bool FWD, bool HALF, bool RP = false, bool NOTW = false>
   static FFC_FN void outer_stage_tile(int L, Unit un, float s_fwd = 1.0f, Pass ps = Pass()) {
-    const i32 lane = B::opaque(B::lane());
     const int w = un.wq;
-    const i32 j = lane & 31, hi = lane >> 5;
     constexpr int ms_lim = (FWD && HALF && GEO::N1 == 32) ? 1 : 2;      // a whole K-step of dead rows (32-point digit)
-    // tile-local row R = 4*hi + c (c a compile-time constant with bit 2 clear) -> column set
-    // s1 = c / N1 and E row rw = c % N1 + 4*hi.  e_off = row term + swizzled column term, so every
-    // access below is (one of S1 lane-dependent bases) + immediate.
+    const i32 lane = B::opaque(B::lane());
+    const i32 j = lane & 31, hi = lane >> 5;
     i32 colb[GEO::S1];
 #pragma unroll
     for (int s = 0; s < GEO::S1; s++)
@@ -1241,9 +1255,8 @@ struct Body {
 #pragma unroll
           for (int hf = 0; hf < 2; hf++) {
             const int e = 2 * d + hf;
-            const int c = 16 * ms + 8 * (e >> 2) + (e & 3);
-            const int s1 = c / GEO::N1, rwc = c % GEO::N1;
-            i32 off = colt[s1] + rwc * (GEO::Mi * 2);
+            const int c = kslot_row(ms, 0, e);
+            i32 off = colt[c / GEO::N1] + row_byte(c);
             // no length mask: rows_store zero-fills every E row this stage reads (HALF never reads the dead rows)
             if (FWD && HALF && row_dead(c)) { vr[hf] = B::uconst(0); vi[hf] = B::uconst(0); continue; }
             vr[hf] = B::lds_r16(off); vi[hf] = B::lds_r16(off + GEO::PLANE);
@@ -1256,29 +1269,23 @@ struct Body {
       re = B::a16_zero(); im = B::a16_zero();
       cmm<!FWD, false>(re, im, op, F1, ms_lim);
       if (FWD && !NOTW) {
-        // s_fwd * W_N^{m*k1}: registers <-> rows k1 = 4*hi + {0..3} + 8*{0..3} (mod N1), lane/tile <-> column m
         // (two chains here: with one -- twiddle16 -- the recomputing full-length backward of fft 32768 spilled one value into a0, build.py check_agpr)
 #pragma unroll
-        for (int half = 0; half < 2; half++) {     // accumulator registers 0-7 / 8-15 (rows +16)
-          const int s1 = (16 * half) / GEO::N1;     // second half: next column set when N1 == 16
-          i32 m = j * 4 + (s1 * 128 + w * 128 * GEO::S1 + t);
-          i32 k0 = hi * 4 + ((16 * half) % GEO::N1);
+        for (int half = 0; half < 2; half++) {
           F2 tr[4], ti[4];
-          if constexpr (RP) chain8p(m * (k0 * ps.R + ps.k0), m * ps.R, -1.0f, s_fwd, tr, ti, GEO::N * ps.R - 1, 1.0f / (float)(GEO::N * ps.R));
-          else chain8p(m * k0, m, -1.0f, s_fwd, tr, ti);
+          outer_fwd_chain<RP>(half, j, hi, w, t, s_fwd, ps, tr, ti);
           apply8(re, im, half, tr, ti);
         }
       }
 #pragma unroll
       for (int r = 0; r < 16; r += 2) {
-        if (!FWD && HALF && row_dead((r & 3) + 8 * (r >> 2))) continue;   // rows beyond L: never stored
+        if (!FWD && HALF && row_dead(acc_row(r, 0))) continue;   // rows beyond L: never stored
         u32 vr = B::template pack<DT>(re[r], re[r + 1]);
         u32 vi = B::template pack<DT>(im[r], im[r + 1]);
 #pragma unroll
         for (int q = 0; q < 2; q++) {
-          const int c = ((r + q) & 3) + 8 * ((r + q) >> 2);
-          const int s1 = c / GEO::N1, rwc = c % GEO::N1;
-          i32 off = colt[s1] + rwc * (GEO::Mi * 2);
+          const int c = acc_row(r + q, 0);
+          i32 off = colt[c / GEO::N1] + row_byte(c);
           B::lds_w16(off, q ? (vr >> 16) : vr);
           B::lds_w16(off + GEO::PLANE, q ? (vi >> 16) : vi);
         }
@@ -1367,8 +1374,8 @@ struct Body {
           } else {
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-              if (!FWD && HALF && row_dead((r & 3) + 8 * (r >> 2))) continue;   // rows beyond L: never stored
-              const int c = (r & 3) + 8 * (r >> 2);
+              if (!FWD && HALF && row_dead(acc_row(r, 0))) continue;   // rows beyond L: never stored
+              const int c = acc_row(r, 0);
               const int s1 = c / GEO::N1, rwc = c % GEO::N1;
               i32 off = colb[s1] + (rwc * (GEO::Mi * 2) + 4 * tp);
               B::lds_w32(off, B::template pack<DT>(re0[r], re[r]));
@@ -1381,19 +1388,19 @@ struct Body {
           if (th == 0) {
 #pragma unroll
             for (int q = 0; q < 8; q++) {
-              if (!FWD && HALF && row_dead(((2 * q) & 3) + 8 * ((2 * q) >> 2))) continue;
+              if (!FWD && HALF && row_dead(acc_row(2 * q, 0))) continue;
               s0r[q] = B::template pack<DT>(re[2 * q], re[2 * q + 1]);
               s0i[q] = B::template pack<DT>(im[2 * q], im[2 * q + 1]);
             }
           } else {
 #pragma unroll
             for (int q = 0; q < 8; q++) {
-              if (!FWD && HALF && row_dead(((2 * q) & 3) + 8 * ((2 * q) >> 2))) continue;
+              if (!FWD && HALF && row_dead(acc_row(2 * q, 0))) continue;
               u32 p1r = B::template pack<DT>(re[2 * q], re[2 * q + 1]), p1i = B::template pack<DT>(im[2 * q], im[2 * q + 1]);
 #pragma unroll
               for (int o = 0; o < 2; o++) {
                 const int r = 2 * q + o;
-                const int c = (r & 3) + 8 * (r >> 2);
+                const int c = acc_row(r, 0);
                 const int s1 = c / GEO::N1, rwc = c % GEO::N1;
                 i32 off = colb[s1] + (rwc * (GEO::Mi * 2) + 4 * tp);
                 B::lds_w32(off, o ? B::merge_hi(s0r[q], p1r) : B::merge_lo(s0r[q], p1r));
@@ -1487,12 +1494,12 @@ struct Body {
         } else {
 #pragma unroll
           for (int r = 0; r < 16; r++) {
-            if (!FWD && HALF && row_dead((r & 3) + 8 * (r >> 2))) continue;   // rows beyond L: never stored
+            if (!FWD && HALF && row_dead(acc_row(r, 0))) continue;   // rows beyond L: never stored
             const u32 vr = B::template pack<DT>(re0[r], re[r]), vi = B::template pack<DT>(im0[r], im[r]);
             if (tp == 0) {
               p0r[r] = vr; p0i[r] = vi;
             } else {
-              const int c = (r & 3) + 8 * (r >> 2);
+              const int c = acc_row(r, 0);
               const int s1 = c / GEO::N1, rwc = c % GEO::N1;
               i32 off = colb[s1] + rwc * (GEO::Mi * 2);
               U2 wr, wi;
@@ -1828,17 +1835,7 @@ struct Body {
       to_op(re, im, op);
       re = B::a16_zero(); im = B::a16_zero();
       cmm2<true>(re, im, op, GA);
-#pragma unroll
-      for (int rq = 0; rq < 4; rq++) {
-        i32 off = R.woff[rq] + tau * (GEO::G * GEO::Mi * 2);
-        U2 vr, vi;
-        vr.x = B::template pack<DT>(re[4 * rq], re[4 * rq + 1]);
-        vr.y = B::template pack<DT>(re[4 * rq + 2], re[4 * rq + 3]);
-        vi.x = B::template pack<DT>(im[4 * rq], im[4 * rq + 1]);
-        vi.y = B::template pack<DT>(im[4 * rq + 2], im[4 * rq + 3]);
-        B::lds_w64(off, vr);
-        B::lds_w64(off + GEO::PLANE, vi);
-      }
+      tile_store(tau, R, re, im);
       return;
     }
     Op op;
@@ -1872,13 +1869,14 @@ struct Body {
     else cmm<true, true>(re, im, op, R.F2);
     // outer inverse twiddle s_inv * W_N^{-(n2*N3+n3)*k1}, generated on the fly (v_sin/v_cos take
     // revolutions; the integer phase m*k1 mod N is exact), so no table traffic in the tile loop
+    // (the same chains: oi_twiddle, and inner_tile2x for two tiles)
     if constexpr (GEO::OUTER) {
       // registers <-> V = (sV, n3) = 4*hi + {0..3} + 8*{0..3}; lane <-> (sU, n2); E row k1 = tau*G + sU*SV + sV
       const i32 sUl = c / GEO::N2, mlane = (c % GEO::N2) * GEO::N3;
       if (dbg & 1) {
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-          i32 V = hi * 4 + ((r & 3) + 8 * (r >> 2));
+          i32 V = hi * 4 + acc_row(r, 0);
           i32 k1 = sUl * GEO::SV + V / GEO::N3 + tau * GEO::G;
           f32 tr, ti;
           cis_rev(B::mul24(mlane + V % GEO::N3, k1), 1.0f, &tr, &ti);
@@ -1893,7 +1891,7 @@ struct Body {
         i32 n30 = hi * 4;
         if constexpr (RP) {
           i32 kk = k1 * ps.R + ps.k0;
-          twiddle16(re, im, B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, GEO::N * ps.R - 1, 1.0f / (float)(GEO::N * ps.R));
+          twiddle16(re, im, B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, rp_nmask(ps), rp_inv_n(ps));
         } else {
           twiddle16(re, im, B::mul24(mlane + n30, k1), k1, 1.0f, s_inv);
         }
@@ -1907,25 +1905,14 @@ struct Body {
         // conj(W^{m k1}) = cos + i sin; multi-pass: k1 -> k0 + R k1 on the N-point circle
         if constexpr (RP) {
           i32 kk = k1 * ps.R + ps.k0;
-          chain8p(B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, tr, ti, GEO::N * ps.R - 1, 1.0f / (float)(GEO::N * ps.R));
+          chain8p(B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, tr, ti, rp_nmask(ps), rp_inv_n(ps));
         } else {
           chain8p(B::mul24(mlane + n30, k1), k1, 1.0f, s_inv, tr, ti);
         }
         apply8(re, im, half, tr, ti);
       }
     }
-    // write back in place: lane <-> (sU,n2), regs <-> (sV,n3); r&3 = 4 consecutive n3
-#pragma unroll
-    for (int rq = 0; rq < 4; rq++) {
-      i32 off = R.woff[rq] + tau * (GEO::G * GEO::Mi * 2);
-      U2 vr, vi;
-      vr.x = B::template pack<DT>(re[4 * rq], re[4 * rq + 1]);
-      vr.y = B::template pack<DT>(re[4 * rq + 2], re[4 * rq + 3]);
-      vi.x = B::template pack<DT>(im[4 * rq], im[4 * rq + 1]);
-      vi.y = B::template pack<DT>(im[4 * rq + 2], im[4 * rq + 3]);
-      B::lds_w64(off, vr);
-      B::lds_w64(off + GEO::PLANE, vi);
-    }
+    tile_store(tau, R, re, im);
   }
 
   struct KfRegs { U4 v[4]; };
@@ -2112,6 +2099,7 @@ struct Body {
     oi_twiddle<false>(a.s_inv, tauB, reB, imB);
     tile_store(tauB, R, reB, imB);
   }
+  // (the same chains: tile_inv, and inner_tile2x for two tiles)
   template <bool RP = false>
   static FFC_FN void oi_twiddle(float s_inv, int tau, A16& re, A16& im, Pass ps = Pass()) {
     const i32 lane = B::opaque(B::lane());
@@ -2122,7 +2110,7 @@ struct Body {
       i32 n30 = hi * 4;
       if constexpr (RP) {
         i32 kk = k1 * ps.R + ps.k0;
-        twiddle16(re, im, B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, GEO::N * ps.R - 1, 1.0f / (float)(GEO::N * ps.R));
+        twiddle16(re, im, B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, rp_nmask(ps), rp_inv_n(ps));
       } else {
         twiddle16(re, im, B::mul24(mlane + n30, k1), k1, 1.0f, s_inv);
       }
@@ -2136,13 +2124,14 @@ struct Body {
       F2 tr[4], ti[4];
       if constexpr (RP) {
         i32 kk = k1 * ps.R + ps.k0;
-        chain8p(B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, tr, ti, GEO::N * ps.R - 1, 1.0f / (float)(GEO::N * ps.R));
+        chain8p(B::mul24(mlane + n30, kk), kk, 1.0f, s_inv, tr, ti, rp_nmask(ps), rp_inv_n(ps));
       } else {
         chain8p(B::mul24(mlane + n30, k1), k1, 1.0f, s_inv, tr, ti);
       }
       apply8(re, im, half, tr, ti);
     }
   }
+  // write back in place: lane <-> (sU,n2), regs <-> (sV,n3); r&3 = 4 consecutive n3
   static FFC_FN void tile_store(int tau, const InnerRegs& R, const A16& re, const A16& im, int doff = 0) {
 #pragma unroll
     for (int rq = 0; rq < 4; rq++) {
@@ -2409,6 +2398,7 @@ struct Body {
     reB = B::a16_zero(); imB = B::a16_zero();
     cmm<true, true>(reB, imB, opB, R.F2);
     // outer inverse twiddle: one chain per accumulator half, applied to both units' tiles
+    // (the one-tile forms of the same chains: tile_inv and oi_twiddle)
     {
       const i32 lane = B::opaque(B::lane());
       const i32 c = lane & 31, hi = lane >> 5;
