@@ -79,3 +79,38 @@ extern "C" int ffc_kernel_ifft_grad_c_slabs(const ffc_plan* p, const void* slabs
   a.R = p->hp.R;
   return ffc_dispatch<DkLaunch>(p->hp.N, DT_BF16, a, (hipStream_t)stream);
 }
+
+// two-tensor form (bidirectional filters): dk = row[:Lk] and dk_rev[m] = row[N-1-m], m < Lr, from one inverse (Modes::dkifft on DkBiArgs)
+template <class GEO, int DT>
+__global__ __launch_bounds__(GEO::WGW * 64, 2) void dkifft_bi_kernel(DkBiArgs a) {
+  Modes<DevB, GEO, DT>::dkifft(a, blockIdx.x);
+}
+template <class GEO, int DT>
+struct DkBiLaunch {
+  static int run(const DkBiArgs& a, hipStream_t st) {
+    using BD = Body<DevB, GEO, DT>;
+    const int lds = GEO::LDS_BYTES + ((!GEO::OUTER && a.R > 1) ? a.R * BD::IPASS_BYTES : 0);   // inner-only multi-pass tables
+    const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
+    return ffc_launch(dkifft_bi_kernel<GEO, DT>, "dkifft_bi_kernel", (nunits + GEO::UPW - 1) / GEO::UPW, GEO::WGW * 64,
+                      GEO::LDS_BYTES + (GEO::OUTER ? 0 : 2 * BD::IPASS_BYTES), lds, st, a);
+  }
+};
+
+extern "C" int ffc_kernel_ifft_grad_bi(const ffc_plan* p, const void* ws, int64_t B, int64_t H, int64_t Lk, float* dk, int64_t Lr,
+                                       float* dk_rev, void* stream) {
+  if (!p || !ws || !dk || !dk_rev) return ffc_fail("null arg");
+  if (H <= 0 || Lk <= 0 || Lk > p->hp.N) return ffc_fail("dk must be (H, Lk) with 0 < Lk <= fft_size");
+  if (Lr <= 0 || Lr > p->hp.N) return ffc_fail("dk_rev must be (H, Lr) with 0 < Lr <= fft_size");
+  if (H * Lk >= ((int64_t)1 << 31) || H * Lr >= ((int64_t)1 << 31)) return ffc_fail("dk too large");
+  int nchunk, ppc;
+  ffc_choose_chunks(p, (int)H, (int)((B + 1) / 2), &nchunk, &ppc);
+  DkBiArgs a{};
+  // always bf16 arithmetic, as ffc_kernel_ifft_grad
+  a.ws = (const float*)ws; a.dk = dk; a.dkr = dk_rev; a.tab = p->d_blob_bf; a.t = p->hp_bf.tabs; a.H = (int)H; a.Lk = (int)Lk; a.Lr = (int)Lr;
+  a.nslab = nchunk;
+  a.scale = (float)(1.0 / p->hp.s_fwd); a.s_inv = (float)p->hp_bf.s_inv;   // tile_inv applies s_inv = 1/(N s_fwd)
+  a.fast = (Lk % 4 == 0) && (Lr % 4 == 0) && !(((uintptr_t)dk | (uintptr_t)dk_rev) & 15);
+  a.flags = p->env_flags;
+  a.R = p->hp.R;
+  return ffc_dispatch<DkBiLaunch>(p->hp.N, DT_BF16, a, (hipStream_t)stream);
+}

@@ -25,6 +25,15 @@ struct KfArgs {
   const void* xpair;   // optional complex input instead of k: pair-plane tensor (2, H, M) dtype (big FFT sizes)
   int fast;            // Lk % 4 == 0 and 16-byte aligned
   int R;               // > 1: multi-pass size (struct Pass); k_f rows are (head, pass)
+  static constexpr bool BI = false;
+};
+// two-tensor form (bidirectional filters): the row of fft size N is k (first Lk taps) + kr reversed (last Lr taps),
+//   row[n] = (n < Lk ? k[n] : 0) + (N-1-n < Lr ? kr[N-1-n] : 0),  summed in fp32 before the prescale and the rounding.
+// The row has no dead tail: every "rows beyond Lk are zero" shortcut sees the whole fft size.  `fast`: both tensors 16-byte loadable.
+struct KfBiArgs : KfArgs {
+  const float* kr;     // (H, Lr) fp32
+  int Lr;
+  static constexpr bool BI = true;
 };
 
 struct DkfArgs {
@@ -78,6 +87,13 @@ struct DkArgs {
   void* outpair;       // optional complex output instead of dk: pair-plane tensor (2, H, M) dtype (big FFT sizes)
   int fast;
   int R;               // > 1: multi-pass size (struct Pass); slab rows are (head, pass)
+  static constexpr bool BI = false;
+};
+// two-tensor form: dk[n] = row[n] (n < Lk) and dkr[m] = row[N-1-m] (m < Lr) from one inverse; `fast`: both tensors 16-byte storable
+struct DkBiArgs : DkArgs {
+  float* dkr;          // (H, Lr) fp32
+  int Lr;
+  static constexpr bool BI = true;
 };
 
 template <class B, class GEO, int DT>
@@ -114,12 +130,32 @@ struct Modes : Body<B, GEO, DT> {
       for (int q = 0; q < 8; q++) v[q] = B::as_f32(B::g_r32(base, e0 + q, ok && ((n + q) < lim)));
     }
   }
+  // the reversed tensor's share of the same 8 samples: v[q] += kr[j0 + 7 - q], j0 = (fft size - 8) - n (a multiple of 8), zero at or beyond `lim`
+  static FFC_FN void fload8_rev_add(const float* base, i32 hb, i32 j0, int lim, bool fast, pred ok, f32 (&v)[8]) {
+    if (fast) {
+      U4 a = B::g_r128p(base, (hb + j0 + 4) >> 2, ok && ((j0 + 4) < lim));
+      U4 b = B::g_r128p(base, (hb + j0) >> 2, ok && (j0 < lim));
+      v[0] = v[0] + B::as_f32(a.w); v[1] = v[1] + B::as_f32(a.z); v[2] = v[2] + B::as_f32(a.y); v[3] = v[3] + B::as_f32(a.x);
+      v[4] = v[4] + B::as_f32(b.w); v[5] = v[5] + B::as_f32(b.z); v[6] = v[6] + B::as_f32(b.y); v[7] = v[7] + B::as_f32(b.x);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; q++) v[q] = v[q] + B::as_f32(B::g_r32(base, hb + j0 + (7 - q), ok && ((j0 + (7 - q)) < lim)));
+    }
+  }
+  // the row length that the dead-row shortcuts see: Lk, or the whole fft size in the two-tensor forms
+  template <class KA>
+  static FFC_FN int live_len(const KA& a, int full) {
+    if constexpr (KA::BI) return full; else return a.Lk;
+  }
   // 16-byte path of k_rows_in: every load of the wave's slice first (clamped, unconditional), then the rounding and the LDS writes.
   // The loop below it consumes each chunk's two loads before it requests the next chunk's: 8 memory round trips in a row for the
   // filter row of a head -- in the forward launch that transforms its own filter (kfft_head) that was most of the step's head time.
-  static FFC_FN void k_rows_in_fast(const KfArgs& a, int unit_id, Unit un) {
+  template <class KA>
+  static FFC_FN void k_rows_in_fast(const KA& a, int unit_id, Unit un) {
+    constexpr bool BI = KA::BI;
     const i32 lane = B::opaque(B::lane());
     U4 A[BD::NCH], Bq[BD::NCH];
+    U4 Ar[BI ? BD::NCH : 1], Br[BI ? BD::NCH : 1];      // two-tensor form: the reversed tensor's pieces (samples n+3..n, n+7..n+4)
 #pragma unroll
     for (int i = 0; i < BD::NCH; i++) {
       // (no skip for chunks beyond Lk: a branch per chunk would put every chunk's loads into a flow block of their own, with a
@@ -132,6 +168,11 @@ struct Modes : Body<B, GEO, DT> {
       i32 hb = B::imin(hd, a.H - 1) * a.Lk;
       A[i] = B::g_r128(a.k, (hb + B::imin(n, a.Lk - 4)) >> 2);
       Bq[i] = B::g_r128(a.k, (hb + B::imin(n + 4, a.Lk - 4)) >> 2);
+      if constexpr (BI) {
+        i32 hr = B::imin(hd, a.H - 1) * a.Lr, j0 = (GEO::N - 8) - n;
+        Ar[i] = B::g_r128(a.kr, (hr + B::imin(j0 + 4, a.Lr - 4)) >> 2);
+        Br[i] = B::g_r128(a.kr, (hr + B::imin(j0, a.Lr - 4)) >> 2);
+      }
     }
     B::sched_fence();
 #pragma unroll
@@ -144,7 +185,7 @@ struct Modes : Body<B, GEO, DT> {
       if constexpr (GEO::OUTER) { hd = row * 0 + unit_id; n = row * GEO::Mi + m; }
       else { hd = row + unit_id * GEO::G; n = m; }
       U4 o;
-      if (GEO::OUTER && ((i * 64) / BD::CPR) * GEO::Mi >= a.Lk) {
+      if (!BI && GEO::OUTER && ((i * 64) / BD::CPR) * GEO::Mi >= a.Lk) {
         o.x = B::uconst(0); o.y = B::uconst(0); o.z = B::uconst(0); o.w = B::uconst(0);
       } else {
         pred oka = (hd < a.H) && (n < a.Lk), okb = (hd < a.H) && ((n + 4) < a.Lk);
@@ -154,6 +195,14 @@ struct Modes : Body<B, GEO, DT> {
         v[2] = B::as_f32(B::sel(oka, A[i].z, zz)); v[3] = B::as_f32(B::sel(oka, A[i].w, zz));
         v[4] = B::as_f32(B::sel(okb, Bq[i].x, zz)); v[5] = B::as_f32(B::sel(okb, Bq[i].y, zz));
         v[6] = B::as_f32(B::sel(okb, Bq[i].z, zz)); v[7] = B::as_f32(B::sel(okb, Bq[i].w, zz));
+        if constexpr (BI) {
+          i32 j0 = (GEO::N - 8) - n;
+          pred okc = (hd < a.H) && ((j0 + 4) < a.Lr), okd = (hd < a.H) && (j0 < a.Lr);
+          v[0] = v[0] + B::as_f32(B::sel(okc, Ar[i].w, zz)); v[1] = v[1] + B::as_f32(B::sel(okc, Ar[i].z, zz));
+          v[2] = v[2] + B::as_f32(B::sel(okc, Ar[i].y, zz)); v[3] = v[3] + B::as_f32(B::sel(okc, Ar[i].x, zz));
+          v[4] = v[4] + B::as_f32(B::sel(okd, Br[i].w, zz)); v[5] = v[5] + B::as_f32(B::sel(okd, Br[i].z, zz));
+          v[6] = v[6] + B::as_f32(B::sel(okd, Br[i].y, zz)); v[7] = v[7] + B::as_f32(B::sel(okd, Br[i].x, zz));
+        }
 #pragma unroll
         for (int q8 = 0; q8 < 8; q8++) v[q8] = v[q8] * a.prescale;
         u32 p0 = B::template pack<DT>(v[0], v[1]), p1 = B::template pack<DT>(v[2], v[3]);
@@ -165,7 +214,8 @@ struct Modes : Body<B, GEO, DT> {
       B::lds_w128(off + GEO::PLANE, z, B::ptrue());
     }
   }
-  static FFC_FN void k_rows_in(const KfArgs& a, int unit_id, Unit un) {
+  template <class KA>
+  static FFC_FN void k_rows_in(const KA& a, int unit_id, Unit un) {
     if (a.fast) { k_rows_in_fast(a, unit_id, un); return; }
     const i32 lane = B::opaque(B::lane());
 #pragma unroll
@@ -180,6 +230,7 @@ struct Modes : Body<B, GEO, DT> {
       pred ok = hd < a.H;
       f32 v[8];
       fload8(a.k, hd * a.Lk + n, n, a.Lk, a.fast != 0, ok, v);
+      if constexpr (KA::BI) fload8_rev_add(a.kr, hd * a.Lr, (GEO::N - 8) - n, a.Lr, a.fast != 0, ok, v);
 #pragma unroll
       for (int q8 = 0; q8 < 8; q8++) v[q8] = v[q8] * a.prescale;
       U4 o;
@@ -192,9 +243,10 @@ struct Modes : Body<B, GEO, DT> {
     }
   }
   // multi-pass sizes: E row n1 = sum_n0 W_R^{n0 k0} k[n0 M + n1 Mi + m] (fp32 sums; (-i)^q (w + 0i) = (w,0),(0,-w),(-w,0),(0,w))
-  static FFC_FN void k_rows_in_rp(const KfArgs& a, int unit_id, Unit un, Pass ps) {
+  template <class KA>
+  static FFC_FN void k_rows_in_rp(const KA& a, int unit_id, Unit un, Pass ps) {
     const i32 lane = B::opaque(B::lane());
-    const int n0max = (a.Lk + GEO::N - 1) / GEO::N;
+    const int n0max = (live_len(a, GEO::N * ps.R) + GEO::N - 1) / GEO::N;
 #pragma unroll
     for (int i = 0; i < BD::NCH; i++) {
       i32 idx = lane + i * 64;
@@ -210,6 +262,7 @@ struct Modes : Body<B, GEO, DT> {
       for (int n0 = 0; n0 < n0max; n0++) {
         f32 w[8];
         fload8(a.k, hd * a.Lk + n + n0 * GEO::N, n + n0 * GEO::N, a.Lk, a.fast != 0, ok, w);
+        if constexpr (KA::BI) fload8_rev_add(a.kr, hd * a.Lr, (GEO::N * ps.R - 8) - (n + n0 * GEO::N), a.Lr, a.fast != 0, ok, w);
         const int q = (n0 * ps.k0 * (4 / ps.R)) & 3;
         const float s = (q == 0 || q == 3) ? a.prescale : -a.prescale;
 #pragma unroll
@@ -275,7 +328,8 @@ struct Modes : Body<B, GEO, DT> {
     }
   }
   // one workgroup: UPW units (heads, or tiles of G heads)
-  static FFC_FN void kfft(const KfArgs& a, int wg) {
+  template <class KA>
+  static FFC_FN void kfft(const KA& a, int wg) {
     BD::setup_tables(a.tab, a.t);
     const int wv = B::wave();
     Unit un;
@@ -293,7 +347,7 @@ struct Modes : Body<B, GEO, DT> {
         for (int k0 = 0; k0 < a.R; k0++) {
           const Pass ps = make_pass(a.tab, a.t, a.R, k0);
           if (act) {
-            if (a.xpair) {       // complex input (pair-plane tensor (2, H, R*M)): inner k_f rows of the big FFT sizes
+            if (!KA::BI && a.xpair) {       // complex input (pair-plane tensor (2, H, R*M)): inner k_f rows of the big FFT sizes
               ConvArgs cv{};
               cv.u = a.xpair; cv.B = 2; cv.H = a.H; cv.L = GEO::N * a.R; cv.fast = 1; cv.sbu = (int64_t)a.H * cv.L;
               BD::template rows_in_rp<BD::NCH>(cv, unit_id, 0, un, ps);
@@ -301,7 +355,7 @@ struct Modes : Body<B, GEO, DT> {
               k_rows_in_rp(a, unit_id, un, ps);
             }
             B::lds_fence();
-            BD::template outer_stage<true, false, true>(a.Lk, un, a.s_fwd, ps);
+            BD::template outer_stage<true, false, true>(live_len(a, GEO::N * a.R), un, a.s_fwd, ps);
           }
           B::barrier();
           if (act) {
@@ -319,7 +373,7 @@ struct Modes : Body<B, GEO, DT> {
     }
     if constexpr (GEO::OUTER) {
       if (act) {
-        if (a.xpair) {
+        if (!KA::BI && a.xpair) {
           ConvArgs cv{};
           cv.u = a.xpair; cv.B = 2; cv.H = a.H; cv.L = GEO::N; cv.fast = 1; cv.sbu = (int64_t)a.H * GEO::N;
           BD::rows_in(cv, unit_id, 0, un);
@@ -327,8 +381,8 @@ struct Modes : Body<B, GEO, DT> {
           k_rows_in(a, unit_id, un);
         }
         B::lds_fence();
-        if ((GEO::N1 / 2) * GEO::Mi >= a.Lk) BD::template outer_stage<true, true>(a.Lk, un, a.s_fwd);
-        else BD::template outer_stage<true, false>(a.Lk, un, a.s_fwd);
+        if (!KA::BI && (GEO::N1 / 2) * GEO::Mi >= a.Lk) BD::template outer_stage<true, true>(a.Lk, un, a.s_fwd);
+        else BD::template outer_stage<true, false>(live_len(a, GEO::N), un, a.s_fwd);
       }
       B::barrier();
       if (act) {
@@ -1422,7 +1476,29 @@ struct Modes : Body<B, GEO, DT> {
 #pragma unroll
     for (int r = 0; r < 16; r++) { re[r] = re[r] * a.scale; im[r] = im[r] * a.scale; }
   }
-  static FFC_FN void dk_rows_out(const DkArgs& a, int unit_id, Unit un) {
+  // the reversed tensor's share of 8 samples v[0..7] at n: dkr[j0 + 7 - q] (+)= v[q], j0 = (fft size - 8) - n
+  static FFC_FN void fstore8_rev(float* base, i32 hb, i32 j0, int lim, bool fast, pred ok, bool add, f32 (&v)[8]) {
+    if (add) {
+      f32 old[8];
+#pragma unroll
+      for (int q = 0; q < 8; q++) old[q] = B::fconst(0.f);
+      fload8_rev_add(base, hb, j0, lim, fast, ok, old);
+#pragma unroll
+      for (int q = 0; q < 8; q++) v[q] = v[q] + old[q];
+    }
+    if (fast) {
+      U4 s0, s1;
+      s0.x = B::as_u32(v[3]); s0.y = B::as_u32(v[2]); s0.z = B::as_u32(v[1]); s0.w = B::as_u32(v[0]);
+      s1.x = B::as_u32(v[7]); s1.y = B::as_u32(v[6]); s1.z = B::as_u32(v[5]); s1.w = B::as_u32(v[4]);
+      B::g_w128(base, (hb + j0 + 4) >> 2, s0, ok && ((j0 + 4) < lim));
+      B::g_w128(base, (hb + j0) >> 2, s1, ok && (j0 < lim));
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; q++) B::g_w32(base, hb + j0 + (7 - q), B::as_u32(v[q]), ok && ((j0 + (7 - q)) < lim));
+    }
+  }
+  template <class KA>
+  static FFC_FN void dk_rows_out(const KA& a, int unit_id, Unit un) {
     const i32 lane = B::opaque(B::lane());
 #pragma unroll
     for (int i = 0; i < BD::NCH; i++) {
@@ -1451,12 +1527,14 @@ struct Modes : Body<B, GEO, DT> {
 #pragma unroll
         for (int q = 0; q < 8; q++) B::g_w32(a.dk, e0 + q, B::as_u32(v[q]), ok && ((n + q) < a.Lk));
       }
+      if constexpr (KA::BI) fstore8_rev(a.dkr, hd * a.Lr, (GEO::N - 8) - n, a.Lr, a.fast != 0, ok, false, v);
     }
   }
   // multi-pass sizes: dk[n0 M + m] (+)= Re(i^q y_k0[m]) = {r, -s, -r, s}[q], q = n0 k0 4/R; fp32 accumulation over the passes
-  static FFC_FN void dk_rows_out_rp(const DkArgs& a, int unit_id, Unit un, Pass ps) {
+  template <class KA>
+  static FFC_FN void dk_rows_out_rp(const KA& a, int unit_id, Unit un, Pass ps) {
     const i32 lane = B::opaque(B::lane());
-    const int n0max = (a.Lk + GEO::N - 1) / GEO::N;
+    const int n0max = (live_len(a, GEO::N * ps.R) + GEO::N - 1) / GEO::N;
 #pragma unroll
     for (int i = 0; i < BD::NCH; i++) {
       i32 idx = lane + i * 64;
@@ -1483,6 +1561,11 @@ struct Modes : Body<B, GEO, DT> {
         for (int k = 0; k < 4; k++) {
           v[2 * k] = B::template unpack_lo<DT>(w[pl][k]) * sg; v[2 * k + 1] = B::template unpack_hi<DT>(w[pl][k]) * sg;
         }
+        f32 vr[8];         // two-tensor form: the pass's own share once more, for the reversed tensor's read-add-write
+        if constexpr (KA::BI) {
+#pragma unroll
+          for (int k = 0; k < 8; k++) vr[k] = v[k];
+        }
         if (ps.k0 > 0) {
           f32 old[8];
           fload8(a.dk, e0, n, a.Lk, a.fast != 0, ok, old);
@@ -1499,10 +1582,12 @@ struct Modes : Body<B, GEO, DT> {
 #pragma unroll
           for (int k = 0; k < 8; k++) B::g_w32(a.dk, e0 + k, B::as_u32(v[k]), ok && ((n + k) < a.Lk));
         }
+        if constexpr (KA::BI) fstore8_rev(a.dkr, hd * a.Lr, (GEO::N * ps.R - 8) - n, a.Lr, a.fast != 0, ok, ps.k0 > 0, vr);
       }
     }
   }
-  static FFC_FN void dkifft(const DkArgs& a, int wg) {
+  template <class KA>
+  static FFC_FN void dkifft(const KA& a, int wg) {
     BD::setup_tables(a.tab, a.t);
     const int wv = B::wave();
     Unit un;
@@ -1529,9 +1614,9 @@ struct Modes : Body<B, GEO, DT> {
           }
           B::barrier();
           if (act) {
-            BD::template outer_stage<false, false, true>(a.Lk, un, 1.0f, ps);
+            BD::template outer_stage<false, false, true>(live_len(a, GEO::N * a.R), un, 1.0f, ps);
             B::lds_fence();
-            if (a.outpair) {     // complex output (pair-plane tensor (2, H, R*M) dtype) accumulated over the passes
+            if (!KA::BI && a.outpair) {     // complex output (pair-plane tensor (2, H, R*M) dtype) accumulated over the passes
               ConvArgs cv{};
               cv.y = a.outpair; cv.B = 2; cv.H = a.H; cv.L = GEO::N * a.R; cv.fast = 1; cv.sby = (int64_t)a.H * cv.L;
               BD::template rows_out_rp<BD::NCH>(cv, unit_id, 0, un, ps);
@@ -1555,9 +1640,9 @@ struct Modes : Body<B, GEO, DT> {
       }
       B::barrier();
       if (act) {
-        BD::template outer_stage<false, false>(a.Lk, un);
+        BD::template outer_stage<false, false>(live_len(a, GEO::N), un);
         B::lds_fence();
-        if (a.outpair) {
+        if (!KA::BI && a.outpair) {
           ConvArgs cv{};
           cv.y = a.outpair; cv.B = 2; cv.H = a.H; cv.L = GEO::N; cv.fast = 1; cv.sby = (int64_t)a.H * GEO::N;
           BD::rows_out(cv, unit_id, 0, un);

@@ -447,6 +447,14 @@ template <class GEO, int DT> struct KfRun {
     return 0;
   }
 };
+template <class GEO, int DT> struct KfBiRun {
+  static int run(const KfBiArgs& a) {
+    const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
+    for (int wg = 0; wg < (nunits + GEO::UPW - 1) / GEO::UPW; wg++)
+      run_wg(GEO::WGW, sim_lds<GEO>(), [&]() { Modes<SimB, GEO, DT>::kfft(a, wg); });
+    return 0;
+  }
+};
 // dkf = true: dkf_kernel / dkf_rp_kernel / dkf_kernel_small; false: bwd_kernel / bwd_rp_kernel / bwd_kernel_small (the library runs the
 // saved-spectra form of the fused sizes as its own instantiation, ZM = 1: ffc_k_bwdz.hip)
 template <class GEO, int DT, bool DKF>
@@ -502,6 +510,14 @@ template <class GEO, int DT> struct DkfRun { static int run(const DkfArgs& d) { 
 template <class GEO, int DT> struct BwdRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, false>(d); } };
 template <class GEO, int DT> struct DkRun {
   static int run(const DkArgs& a) {
+    const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
+    for (int wg = 0; wg < (nunits + GEO::UPW - 1) / GEO::UPW; wg++)
+      run_wg(GEO::WGW, sim_lds<GEO>(), [&]() { Modes<SimB, GEO, DT>::dkifft(a, wg); });
+    return 0;
+  }
+};
+template <class GEO, int DT> struct DkBiRun {
+  static int run(const DkBiArgs& a) {
     const int nunits = GEO::OUTER ? a.H : (a.H + GEO::G - 1) / GEO::G;
     for (int wg = 0; wg < (nunits + GEO::UPW - 1) / GEO::UPW; wg++)
       run_wg(GEO::WGW, sim_lds<GEO>(), [&]() { Modes<SimB, GEO, DT>::dkifft(a, wg); });
@@ -890,6 +906,20 @@ int ffcsim_kernel_fft(int N, int dtype, const float* k, int H, int Lk, void* kf)
   return dispatch<KfRun>(N, dtype, a);
 }
 
+// two-tensor form (ffc_kernel_fft_bi): k (H, Lk) and k_rev (H, Lr)
+int ffcsim_kernel_fft_bi(int N, int dtype, const float* k, int Lk, const float* k_rev, int Lr, int H, void* kf) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (!k || !k_rev || Lk <= 0 || Lk > N || Lr <= 0 || Lr > N) return -1;
+  KfBiArgs a{};
+  a.k = k; a.kr = k_rev; a.kf = kf; a.tab = p.blob.data(); a.t = p.tabs; a.H = H; a.Lk = Lk; a.Lr = Lr;
+  a.s_fwd = (float)p.s_fwd;
+  a.prescale = dtype == DT_F16 ? 256.f : 1.f;
+  a.scale = (float)(p.s_k / p.s_fwd) / a.prescale; a.fast = (Lk % 4 == 0) && (Lr % 4 == 0) && !g_force_slow;
+  a.R = p.R;
+  return dispatch<KfBiRun>(N, dtype, a);
+}
+
 // ws must hold nchunk*UPW*H*NT*2048 floats
 int ffcsim_conv_bwd_dkf(int N, int dtype, const void* dout, const void* u, const void* pregate, const void* postgate,
                         float* ws, int B, int H, int L, int nchunk) {
@@ -972,6 +1002,21 @@ int ffcsim_kernel_ifft_grad(int N, int dtype, const float* ws, int nslab, int H,
   a.fast = (Lk % 4 == 0) && !g_force_slow;
   a.R = p.R;
   return dispatch<DkRun>(N, dtype, a);
+}
+
+// two-tensor form (ffc_kernel_ifft_grad_bi): dk (H, Lk) and dk_rev (H, Lr) from one inverse
+int ffcsim_kernel_ifft_grad_bi(int N, int dtype, const float* ws, int nslab, int H, int Lk, float* dk, int Lr, float* dk_rev) {
+  HostPlan p;
+  (void)dtype;                      // bf16 arithmetic, as ffcsim_kernel_ifft_grad
+  dtype = DT_BF16;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (!dk || !dk_rev || Lk <= 0 || Lk > N || Lr <= 0 || Lr > N) return -1;
+  DkBiArgs a{};
+  a.ws = ws; a.dk = dk; a.dkr = dk_rev; a.tab = p.blob.data(); a.t = p.tabs; a.H = H; a.Lk = Lk; a.Lr = Lr; a.nslab = nslab;
+  a.scale = (float)(1.0 / p.s_fwd); a.s_inv = (float)p.s_inv;
+  a.fast = (Lk % 4 == 0) && (Lr % 4 == 0) && !g_force_slow;
+  a.R = p.R;
+  return dispatch<DkBiRun>(N, dtype, a);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@ def lib():
         L.ffc_plan_kf_scale.argtypes = [c_vp]; L.ffc_plan_kf_scale.restype = ctypes.c_double
         L.ffc_plan_kf_index.argtypes = [c_vp, c_vp]
         L.ffc_kernel_fft.argtypes = [c_vp, c_vp, c_i64, c_i64, c_vp, c_vp]
+        L.ffc_kernel_fft_bi.argtypes = [c_vp, c_vp, c_i64, c_vp, c_i64, c_i64, c_vp, c_vp]
         L.ffc_kf_pack.argtypes = [c_vp, c_vp, c_i64, c_vp, c_vp]
         L.ffc_conv_fwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_vp]
         L.ffc_conv_fwd_sparse.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_vp]
@@ -47,6 +48,7 @@ def lib():
         L.ffc_conv_bwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd_gated.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_kernel_ifft_grad.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]
+        L.ffc_kernel_ifft_grad_bi.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]
         L.ffc_kernel_ifft_grad_slabs.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]
         c_f = ctypes.c_float
         L.ffc_outer_pass.argtypes = [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, c_i64, c_f, c_vp]

@@ -276,6 +276,47 @@ def _kernel_fft(plan, k):
     return kf
 
 
+def _kernel_fft_bi(plan, k, k_rev):
+    """bidirectional filter from its two tensors, k (H, Lk) and k_rev (H, Lr) -> k_f of the row k + reversed k_rev (ffc_kernel_fft_bi)"""
+    H = k.shape[0]
+    kf = torch.empty(H, plan.kf_elems, 2, dtype=plan.dtype, device=k.device)
+    k32 = k.detach().to(torch.float32).contiguous()
+    r32 = k_rev.detach().to(torch.float32).contiguous()
+    _lib.check(_lib.lib().ffc_kernel_fft_bi(plan.handle, _lib.ptr(k32), k32.shape[-1], _lib.ptr(r32), r32.shape[-1], H, _lib.ptr(kf),
+                                            _lib.stream_ptr()), "ffc_kernel_fft_bi")
+    return kf
+
+
+def _ifft_grad_bi(plan, ws, B, H, Lk, Lr, device):
+    """dk (H, Lk) and dk_rev (H, Lr) fp32 from the dk_f partial sums in one inverse (ffc_kernel_ifft_grad_bi)"""
+    dk = torch.empty(H, Lk, dtype=torch.float32, device=device)
+    dkr = torch.empty(H, Lr, dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().ffc_kernel_ifft_grad_bi(plan.handle, _lib.ptr(ws), B, H, Lk, _lib.ptr(dk), Lr, _lib.ptr(dkr), _lib.stream_ptr()),
+               "ffc_kernel_ifft_grad_bi")
+    return dk, dkr
+
+
+def _compose_k_full(k, k_rev, n):
+    """the n-tap row of a bidirectional filter by differentiable torch ops (the routes without the two-tensor kernels):
+    k_full[:, i] = (i < Lk ? k[:, i] : 0) + (n-1-i < Lr ? k_rev[:, n-1-i] : 0), fp32"""
+    pad = torch.nn.functional.pad
+    return pad(k.to(torch.float32), (0, n - k.shape[-1])) + pad(k_rev.to(torch.float32).flip(-1), (n - k_rev.shape[-1], 0))
+
+
+def _kf_key2(k, k_rev):
+    """cache key of a filter given as one tensor or as the pair (k, k_rev): covers both tensors"""
+    return _kf_key(k) if k_rev is None else (_kf_key(k), _kf_key(k_rev))
+
+
+def _check_k_rev(what, k_rev, H, seqlen, device):
+    if not torch.is_tensor(k_rev):
+        raise RuntimeError(f"FlashFFTConv: {what} must be a tensor")
+    if k_rev.device != device:
+        raise RuntimeError(f"FlashFFTConv: {what} is on {k_rev.device}, u on {device}")
+    if k_rev.dim() != 2 or k_rev.shape[0] != H or not 1 <= k_rev.shape[-1] <= seqlen:
+        raise RuntimeError(f"FlashFFTConv: {what} must be (H = {H}, Lr) with 1 <= Lr <= fft size {seqlen}")
+
+
 _BIG_ONE_CALL = _os.environ.get("FFC_BIG_ONE_CALL", "1") != "0"      # A/B switch: "0" = kfft_c / conv / bwd / dkifft_c as separate calls
 _ONE_LAUNCH_LEVEL = _os.environ.get("FFC_BIG_ONE_LAUNCH", "1") != "0"      # A/B switch: "0" = one launch per pass (ffc_outer_pass_r)
 
@@ -679,28 +720,40 @@ class _FlashFFTConvFn(torch.autograd.Function):
     # reference: FlashFFTConvFunc (conv.py:563) and GatedFlashFFTConvFunc (conv.py:3236)
 
     @staticmethod
-    def forward(ctx, u, k, mod, pregate, postgate, residual=None):
+    def forward(ctx, u, k, mod, pregate, postgate, residual=None, k_rev=None):
         _check_inputs(mod, u, k, (pregate, postgate))
         if residual is not None:
             _check_residual(u, residual)
+        if k_rev is not None:
+            _check_k_rev("k_rev", k_rev, u.shape[1], mod.seqlen, u.device)
         with _dev_ctx(u.device):      # launches go to u's device and its current stream
-            return _FlashFFTConvFn._forward(ctx, u, k, mod, pregate, postgate, residual)
+            return _FlashFFTConvFn._forward(ctx, u, k, mod, pregate, postgate, residual, k_rev)
 
     @staticmethod
-    def _forward(ctx, u, k, mod, pregate, postgate, residual=None):
+    def _forward(ctx, u, k, mod, pregate, postgate, residual=None, k_rev=None):
         # residual: added in the convolution kernel's output epilogue (fused routes only: FlashFFTConv.forward composes the others)
+        # k_rev: the reversed half of a bidirectional filter, read by the k -> k_f kernel itself (ffc_kernel_fft_bi; fused, unfolded, dense
+        # routes only: FlashFFTConv.forward composes the others).  The filter fills the fft size: no HBM-level routing by length here.
         residual = None if residual is None else residual.contiguous()
         u = u.contiguous()
         pregate = None if pregate is None else pregate.contiguous()
         postgate = None if postgate is None else postgate.contiguous()
         ctx.mod, ctx.k_len, ctx.k_dtype, ctx.gated = mod, k.shape[-1], k.dtype, pregate is not None
         ctx.big = mod._big or mod._route_big(max(u.shape[-1], k.shape[-1]))
+        ctx.rev = None if k_rev is None else (k_rev.shape[-1], k_rev.dtype)
+        if k_rev is not None and (ctx.big or mod._folded or mod._kf_keep is not None):
+            raise RuntimeError("FlashFFTConv: internal: k_rev on a route without the two-tensor kernels")
         kept = None
         if ctx.big:
             out, kf, kept, ctx.fac, ctx.half = _big_forward_routed(mod, u, k, pregate, postgate, any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4)))
         else:
             plan = mod._get_plan(u.device, mod._plan_seqlen)
-            kf = mod._cached_kf(k) if mod.cache_kf and not k.requires_grad else None
+            cache = mod.cache_kf and not k.requires_grad and not (k_rev is not None and k_rev.requires_grad)
+            kf = mod._cached_kf(k, k_rev) if cache else None
+            if kf is None and k_rev is not None:      # k -> k_f as a launch of its own, then the convolution entry points
+                kf = _kernel_fft_bi(plan, k, k_rev)
+                if cache:
+                    mod._kf_cache = (_kf_key2(k, k_rev), kf)
             # one C-ABI call for k -> k_f + the convolution (ffc_conv_fwd_k) unless something sits between the two
             # (a residual takes k -> k_f + ffc_conv_fwd_res: the one-call entry point has no addend)
             one_call = kf is None and not mod._folded and mod._kf_keep is None and residual is None
@@ -763,13 +816,15 @@ class _FlashFFTConvFn(torch.autograd.Function):
     def backward(ctx, dout):
         if not ctx.saved_tensors:
             raise RuntimeError("FlashFFTConv: backward needs module.training=True at forward time")
+        rev = []      # dk_rev, when the call had a k_rev
         with _dev_ctx(ctx.saved_tensors[0].device):
-            grads = _FlashFFTConvFn._backward(ctx, dout)
+            grads = _FlashFFTConvFn._backward(ctx, dout, rev)
         # y = (...) + residual: the residual's gradient is dout itself; the other gradients never see it
-        return grads + (dout if ctx.needs_input_grad[5] else None,)      # (every caller passes the residual slot, None included)
+        # (every caller passes the residual and k_rev slots, None included)
+        return grads + (dout if ctx.needs_input_grad[5] else None, rev[0] if rev else None)
 
     @staticmethod
-    def _backward(ctx, dout):
+    def _backward(ctx, dout, rev_out=None):
         dout = dout.contiguous()
         z = yraw = None
         if ctx.gated:
@@ -795,7 +850,7 @@ class _FlashFFTConvFn(torch.autograd.Function):
         du = torch.empty_like(u)
         dpre = torch.empty_like(u) if ctx.gated else None
         dpost = torch.empty_like(u) if ctx.gated else None
-        if not ctx.mod._folded and ctx.mod._kf_keep is None:
+        if not ctx.mod._folded and ctx.mod._kf_keep is None and ctx.rev is None:
             # one C-ABI call: fused backward (on the saved spectra when there are any) + dk_f -> dk (ffc_conv_bwd_k)
             dk = torch.empty(H, k_len, dtype=torch.float32, device=u.device)
             _lib.check(lib.ffc_conv_bwd_k(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
@@ -823,9 +878,13 @@ class _FlashFFTConvFn(torch.autograd.Function):
             slabs = ws[: (ws.numel() // 4 // nfl) * nfl * 4].view(torch.float32).view(-1, H, plan.kf_elems, 2)
             nslab = lib.ffc_dkf_slab_count(plan.handle, B, H)
             slabs[:nslab].mul_(ctx.mod._kf_mask(plan, torch.float32)[None, None, :, None])
-        dk = torch.empty(H, k_len, dtype=torch.float32, device=u.device)
-        _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, H, k_len, _lib.ptr(dk), _lib.stream_ptr()),
-                   "ffc_kernel_ifft_grad")
+        if ctx.rev is not None:      # both halves of a bidirectional filter's gradient from one inverse
+            dk, dkr = _ifft_grad_bi(plan, ws, B, H, k_len, ctx.rev[0], u.device)
+            rev_out.append(dkr.to(ctx.rev[1]))
+        else:
+            dk = torch.empty(H, k_len, dtype=torch.float32, device=u.device)
+            _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, H, k_len, _lib.ptr(dk), _lib.stream_ptr()),
+                       "ffc_kernel_ifft_grad")
         if ctx.mod._folded:      # chain rule of _periodise_k
             n = ctx.mod.seqlen
             dk = (dk[:, :n] + dk[:, n:])[:, :ctx.k_len]
@@ -931,9 +990,9 @@ class FlashFFTConv(torch.nn.Module):
         re-reads all four input blocks).  fft 65536 stays on its 2 passes at every length (L = 64K: 6.7 vs 7.2)."""
         return self.seqlen == 131072 and not self._big and Lmax > 65536 and 131072 in MULTIPASS_SEQLENS and _ROUTE_BY_LENGTH
 
-    def _cached_kf(self, k):
+    def _cached_kf(self, k, k_rev=None):
         c = self._kf_cache
-        return c[1] if c is not None and c[0] == _kf_key(k) else None
+        return c[1] if c is not None and c[0] == _kf_key2(k, k_rev) else None
 
     def _kf_mask(self, plan, dtype):
         """0/1 mask over k_f's internal positions keeping the natural frequencies |f| < self._kf_keep."""
@@ -966,8 +1025,23 @@ class FlashFFTConv(torch.nn.Module):
             return True
         return _sparse_rows(self, _SeqlenOnly(self._plan_seqlen)) > 0
 
-    def forward(self, u, k, pregate=None, postgate=None, residual=None):
+    def _k_rev_composes(self):
+        """routes without the two-tensor k -> k_f / dk_f -> dk kernels: the HBM-level sizes (a bidirectional filter fills the fft size, so
+        fft 131072 is length-routed to its HBM level too), the folded fft-2048 plan and the frequency-sparse modules"""
+        return bool(self._big or self._folded or self._kf_keep is not None or self._route_big(self.seqlen))
+
+    def forward(self, u, k, pregate=None, postgate=None, residual=None, k_rev=None):
         """y = postgate * conv(u * pregate, k) + residual (gates: both or none; residual optional).
+
+        k_rev (H, Lr), 1 <= Lr <= seqlen, on u's device: the reversed half of a bidirectional filter.  The call is the one on the seqlen-tap row
+            k_full[h, n] = (n < Lk ? k[h, n] : 0) + (seqlen-1-n < Lr ? k_rev[h, seqlen-1-n] : 0)
+        = pad(k, (0, seqlen - Lk)) + pad(flip(k_rev), (seqlen - Lr, 0)): k_rev[m] is the tap at circular lag -(m+1), overlapping taps add (fp32
+        sum before any rounding), and k_rev receives its own gradient dk_rev[h, m] = dk_full[h, seqlen-1-m].  On the fused routes (fft <=
+        131072, not folded, not frequency-sparse, not length-routed to an HBM level) the k -> k_f kernel reads both tensors and the dk_f -> dk
+        kernel writes both gradients: no pad, flip or add kernel on the filter; k -> k_f and dk_f -> dk then run as launches of their own at
+        every size.  Everywhere else -- the HBM-level sizes (fft >= 262144, and fft 131072, which a full-length filter routes to its HBM
+        level), the folded fft-2048 plan, the frequency-sparse modules -- the module builds k_full with those torch ops and calls itself
+        without k_rev: the same function by composition.  The fft size is not fitted to the rows (_fit_seqlen): the filter fills it.
 
         residual (u's shape, dtype and device; a skip connection or a second branch) is added in the convolution kernel's output
         epilogue -- fp32 product and sum, one rounding -- on every fused route (fft <= 131072), with no elementwise kernel behind the
@@ -976,6 +1050,14 @@ class FlashFFTConv(torch.nn.Module):
         frequency-sparse kernel; there the module returns conv(u, k, pregate, postgate) + residual by composition (two roundings)."""
         if pregate is not None or postgate is not None:
             assert pregate is not None and postgate is not None
+        if k_rev is not None:
+            _check_inputs(self, u, k, (pregate, postgate))
+            _check_k_rev("k_rev", k_rev, u.shape[1], self.seqlen, u.device)
+            if self._k_rev_composes():
+                return self(u, _compose_k_full(k, k_rev, self.seqlen), pregate, postgate, residual)
+            if residual is not None:      # (a fused route: its epilogue takes the residual)
+                _check_residual(u, residual)
+            return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, residual, k_rev)
         if self.seqlen > 32768 and torch.is_tensor(u) and torch.is_tensor(k) and u.dim() == 3 and k.dim() == 2:
             n = self._fit_seqlen(u.shape[-1], k.shape[-1])
             if n != self.seqlen:
@@ -984,5 +1066,5 @@ class FlashFFTConv(torch.nn.Module):
             _check_inputs(self, u, k, (pregate, postgate))
             _check_residual(u, residual)
             if self._residual_composes(max(u.shape[-1], k.shape[-1])):
-                return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, None) + residual
-        return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, residual)
+                return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, None, None) + residual
+        return _apply_noting_grad_mode(_FlashFFTConvFn, u, k, self, pregate, postgate, residual, None)

@@ -26,7 +26,8 @@ import torch
 
 from . import _lib
 from .conv import (FlashFFTConv, _check_inputs, _kernel_fft, _periodise_k, _spectrum_buffer, _kf_key, _apply_noting_grad_mode, _recording,
-                   _big_forward_routed, _big_backward, _dev_ctx, _TorchOps)
+                   _big_forward_routed, _big_backward, _dev_ctx, _TorchOps, _kernel_fft_bi, _ifft_grad_bi, _compose_k_full, _kf_key2,
+                   _check_k_rev)
 from . import bigfft as _bigfft
 from .depthwise_1d import FlashDepthWiseConv1d
 
@@ -37,31 +38,41 @@ def _slice_ptr(t, j, D, L):
 
 class _GatedSlicesFn(torch.autograd.Function):
     """y = uc[:, 1] * conv(uc[:, 0] * uc[:, 2], k) [+ conv(uc[:, 2], k_res)] for uc viewed as (B, 3, D, L): x1 = slice 0, x2 = slice 1,
-    v = slice 2."""
+    v = slice 2.  k_rev / k_res_rev: the reversed halves of bidirectional filters (FlashFFTConv.forward), read by the k -> k_f kernel and
+    their gradients written by the dk_f -> dk kernel (unfolded modules only: gated_conv_from_slices composes the others)."""
 
     @staticmethod
-    def forward(ctx, uc, k, mod, k_res=None):
+    def forward(ctx, uc, k, mod, k_res=None, k_rev=None, k_res_rev=None):
         B, D3, L = uc.shape
         D = D3 // 3
         plan = mod._get_plan(uc.device, mod._plan_seqlen)
+        if (k_rev is not None or k_res_rev is not None) and mod._folded:
+            raise RuntimeError("FlashHyenaOp: internal: a reversed filter on a folded plan")
         with torch.cuda.device(uc.device):
-            kf = mod._cached_kf(k) if mod.cache_kf and not k.requires_grad else None      # inference cache, as FlashFFTConv
+            cache = mod.cache_kf and not k.requires_grad and not (k_rev is not None and k_rev.requires_grad)
+            kf = mod._cached_kf(k, k_rev) if cache else None      # inference cache, as FlashFFTConv
             if kf is None:
-                kf = _kernel_fft(plan, _periodise_k(k, mod.seqlen) if mod._folded else k)
-                if mod.cache_kf and not k.requires_grad:
-                    mod._kf_cache = (_kf_key(k), kf)
+                if k_rev is not None:
+                    kf = _kernel_fft_bi(plan, k, k_rev)
+                else:
+                    kf = _kernel_fft(plan, _periodise_k(k, mod.seqlen) if mod._folded else k)
+                if cache:
+                    mod._kf_cache = (_kf_key2(k, k_rev), kf)
             y = torch.empty(B, D, L, dtype=uc.dtype, device=uc.device)
             sb = D3 * L
             kf_res = yu = None
             if k_res is not None:
                 # launch 1: yu = conv(v, k_res), v read in place; its k_f has a cache slot of its own (k and k_res would evict each other)
-                cache_res = mod.cache_kf and not k_res.requires_grad
+                cache_res = mod.cache_kf and not k_res.requires_grad and not (k_res_rev is not None and k_res_rev.requires_grad)
                 c = getattr(mod, "_kf_cache_res", None) if cache_res else None
-                kf_res = c[1] if c is not None and c[0] == _kf_key(k_res) else None
+                kf_res = c[1] if c is not None and c[0] == _kf_key2(k_res, k_res_rev) else None
                 if kf_res is None:
-                    kf_res = _kernel_fft(plan, _periodise_k(k_res, mod.seqlen) if mod._folded else k_res)
+                    if k_res_rev is not None:
+                        kf_res = _kernel_fft_bi(plan, k_res, k_res_rev)
+                    else:
+                        kf_res = _kernel_fft(plan, _periodise_k(k_res, mod.seqlen) if mod._folded else k_res)
                     if cache_res:
-                        mod._kf_cache_res = (_kf_key(k_res), kf_res)
+                        mod._kf_cache_res = (_kf_key2(k_res, k_res_rev), kf_res)
                 yu = torch.empty_like(y)
                 _lib.check(_lib.lib().ffc_conv_fwd_strided(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf_res), None, None, _lib.ptr(yu),
                                                            B, D, L, 0, sb, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_strided")
@@ -89,6 +100,8 @@ class _GatedSlicesFn(torch.autograd.Function):
                                                      sb, sb, sb, 0, _lib.stream_ptr()), "ffc_conv_fwd_z")
         ctx.mod, ctx.k_len, ctx.k_dtype = mod, k.shape[-1], k.dtype
         ctx.res = None if k_res is None else (k_res.shape[-1], k_res.dtype)
+        ctx.rev = None if k_rev is None else (k_rev.shape[-1], k_rev.dtype)
+        ctx.res_rev = None if k_res_rev is None else (k_res_rev.shape[-1], k_res_rev.dtype)
         if mod.training:
             ctx.save_for_backward(*((uc, kf) + (() if z is None else (z, yraw)) + (() if kf_res is None else (kf_res,))))
         return y
@@ -126,9 +139,14 @@ class _GatedSlicesFn(torch.autograd.Function):
                                                       _slice_ptr(duc, 0, D, L), _slice_ptr(duc, 1, D, L), _lib.ptr(ws), B, D, L,
                                                       0, sb, sb, sb, sb, sb, sb, _lib.stream_ptr()), "ffc_conv_bwd_gated_strided")
             k_len = plan.seqlen if mod._folded else ctx.k_len
-            dk = torch.empty(D, k_len, dtype=torch.float32, device=uc.device)
-            _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, k_len, _lib.ptr(dk), _lib.stream_ptr()),
-                       "ffc_kernel_ifft_grad")
+            dk_rev = dk_res_rev = None
+            if ctx.rev is not None:
+                dk, dk_rev = _ifft_grad_bi(plan, ws, B, D, k_len, ctx.rev[0], uc.device)
+                dk_rev = dk_rev.to(ctx.rev[1])
+            else:
+                dk = torch.empty(D, k_len, dtype=torch.float32, device=uc.device)
+                _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, k_len, _lib.ptr(dk), _lib.stream_ptr()),
+                           "ffc_kernel_ifft_grad")
             if mod._folded:
                 n = mod.seqlen
                 dk = (dk[:, :n] + dk[:, n:])[:, :ctx.k_len]
@@ -141,15 +159,19 @@ class _GatedSlicesFn(torch.autograd.Function):
                                                           _lib.ptr(dv), None, None, _lib.ptr(ws), B, D, L, 0, sb, 0, 0, 0, 0, 0,
                                                           _lib.stream_ptr()), "ffc_conv_bwd_gated_strided")
                 kr_len = plan.seqlen if mod._folded else ctx.res[0]
-                dk_res = torch.empty(D, kr_len, dtype=torch.float32, device=uc.device)
-                _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, kr_len, _lib.ptr(dk_res), _lib.stream_ptr()),
-                           "ffc_kernel_ifft_grad")
+                if ctx.res_rev is not None:
+                    dk_res, dk_res_rev = _ifft_grad_bi(plan, ws, B, D, kr_len, ctx.res_rev[0], uc.device)
+                    dk_res_rev = dk_res_rev.to(ctx.res_rev[1])
+                else:
+                    dk_res = torch.empty(D, kr_len, dtype=torch.float32, device=uc.device)
+                    _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, kr_len, _lib.ptr(dk_res), _lib.stream_ptr()),
+                               "ffc_kernel_ifft_grad")
                 if mod._folded:
                     n = mod.seqlen
                     dk_res = (dk_res[:, :n] + dk_res[:, n:])[:, :ctx.res[0]]
                 dk_res = dk_res.to(ctx.res[1])
                 duc[:, 2 * D:].add_(dv)
-        return duc, dk.to(ctx.k_dtype), None, dk_res
+        return duc, dk.to(ctx.k_dtype), None, dk_res, dk_rev, dk_res_rev      # (the caller passes every filter slot, None included)
 
 
 class _GatedSlicesBigFn(torch.autograd.Function):
@@ -214,7 +236,7 @@ class _GatedSlicesBigFn(torch.autograd.Function):
         return duc, dk.to(ctx.k_dtype), None, dk_res
 
 
-def gated_conv_from_slices(conv, uc, k, k_res=None):
+def gated_conv_from_slices(conv, uc, k, k_res=None, k_rev=None, k_res_rev=None):
     """y = x2 * conv(x1 * v, k) [+ conv(v, k_res)] with (x1, x2, v) = uc.split(D, dim=1), uc (B, 3D, L) contiguous, through `conv`
     (a FlashFFTConv).  Every route reads the slices in place and writes the gradients into the slices of one d(uc): the fused kernels
     (fft <= 131072) through their strided launchers, the HBM-level routes (fft >= 262144, fft 131072 with rows longer than half of it)
@@ -224,12 +246,37 @@ def gated_conv_from_slices(conv, uc, k, k_res=None):
     output epilogue on the fused routes and by composition (a second convolution reading v in place, one add) on the HBM-level ones.
     Both convolutions run on ONE module, fitted to the longer of the two filters (_fit_seqlen); the composition conv(v, k, x1, x2,
     residual=conv(v, k_res)) fits each call to its own filter.  Nothing wraps at either size, so the results agree to rounding; they are the
-    same bits when both filters select the same fft size."""
+    same bits when both filters select the same fft size.
+    k_rev / k_res_rev (D, Lr) fp32: the reversed halves of bidirectional filters, FlashFFTConv.forward's k_rev for k and for k_res (M2-BERT
+    builds both filters that way).  On the fused routes the k -> k_f kernel reads the two tensors of a filter and the dk_f -> dk kernel writes
+    both gradients, each filter with its own cache slot; the fft size is conv.seqlen (a bidirectional filter fills it: no fitting).  The
+    HBM-level routes (which include fft 131072 here), folded and frequency-sparse modules and every case that falls back to contiguous
+    copies build the full rows with torch ops (conv._compose_k_full) and run as without the reversed tensors."""
     if uc.dim() != 3 or uc.shape[1] % 3:
         raise RuntimeError("gated_conv_from_slices: uc must be (B, 3*D, L)")
     D, L = uc.shape[1] // 3, uc.shape[2]
     if k_res is not None and (not torch.is_tensor(k_res) or k_res.dim() != 2 or k_res.shape[0] != D):
         raise RuntimeError(f"gated_conv_from_slices: k_res must be (D = {D}, Lk)")
+    if k_rev is not None or k_res_rev is not None:
+        if k_res_rev is not None and k_res is None:
+            raise RuntimeError("gated_conv_from_slices: k_res_rev needs k_res")
+        for what, t in (("k_rev", k_rev), ("k_res_rev", k_res_rev)):
+            if t is not None:
+                _check_k_rev(what, t, D, conv.seqlen, uc.device)
+        N = conv.seqlen
+        wide = (uc.shape[0] - 1) * 3 * D * L + D * L >= 2 ** 31
+        fused = (torch.is_tensor(k) and k.dim() == 2 and not conv._k_rev_composes() and (D * L) % 8 == 0 and uc.is_contiguous() and not wide)
+        if not fused:
+            _check_inputs(conv, uc[:, :D], k, ())
+            if k_res is not None:
+                _check_inputs(conv, uc[:, :D], k_res, ())
+            kk = k if k_rev is None else _compose_k_full(k, k_rev, N)
+            kk_res = k_res if k_res_rev is None else _compose_k_full(k_res, k_res_rev, N)
+            return gated_conv_from_slices(conv, uc, kk, kk_res)
+        _check_inputs(conv, uc[:, :D], k, ())
+        if k_res is not None:
+            _check_inputs(conv, uc[:, :D], k_res, ())
+        return _apply_noting_grad_mode(_GatedSlicesFn, uc, k, conv, k_res, k_rev, k_res_rev)
     # a model built for its longest sequence and run on a shorter one: the smallest fft size that holds the rows (FlashFFTConv._fit_seqlen)
     lk = k.shape[-1] if k_res is None or k.dim() != 2 else max(k.shape[-1], k_res.shape[-1])
     n = conv._fit_seqlen(L, lk) if k.dim() == 2 else conv.seqlen
@@ -258,14 +305,17 @@ def gated_conv_from_slices(conv, uc, k, k_res=None):
     _check_inputs(conv, uc[:, :D], k, ())
     if k_res is not None:
         _check_inputs(conv, uc[:, :D], k_res, ())
-    return _apply_noting_grad_mode(_GatedSlicesBigFn if big else _GatedSlicesFn, uc, k, conv, k_res)
+    if big:
+        return _apply_noting_grad_mode(_GatedSlicesBigFn, uc, k, conv, k_res)
+    return _apply_noting_grad_mode(_GatedSlicesFn, uc, k, conv, k_res, None, None)
 
 
 class FlashHyenaOp(torch.nn.Module):
     """short depthwise conv (k = 3, "same" length) over the 3*D projected channels, then y = x2 * fftconv(x1 * v, k).
 
-    forward(x1x2v, k, k_res=None): x1x2v (B, 3*D, L) bf16/fp16 (the in-projection's output, channels first), k (D, Lk) fp32 -> (B, D, L);
+    forward(x1x2v, k, k_res=None, k_rev=None, k_res_rev=None): x1x2v (B, 3*D, L) bf16/fp16 (the in-projection's output, channels first), k (D, Lk) fp32 -> (B, D, L);
     with k_res (D, Lk2) fp32, y = x2 * fftconv(x1 * v, k) + fftconv(v, k_res) (M2-BERT's residual_long_conv).
+    k_rev / k_res_rev (D, Lr) fp32: the reversed halves of bidirectional filters (FlashFFTConv.forward's k_rev, for k and for k_res).
     `short_filter_weight` (3D, 1, 3) or (3D, 3) and `short_filter_bias` (3D,) are the nn.Conv1d parameters the reference
     callers pass to FlashDepthWiseConv1d (hyenadna_flashfftconv.py:248-261: padding=1, i.e. the [..., :l] crop is a no-op)."""
 
@@ -276,9 +326,9 @@ class FlashHyenaOp(torch.nn.Module):
                                                  device=device, dtype=dtype)
         self.flashfftconv = FlashFFTConv(fft_size, dtype=dtype)
 
-    def forward(self, x1x2v, k, k_res=None):
+    def forward(self, x1x2v, k, k_res=None, k_rev=None, k_res_rev=None):
         uc = self.short_filter(x1x2v)
-        return gated_conv_from_slices(self.flashfftconv, uc, k, k_res)
+        return gated_conv_from_slices(self.flashfftconv, uc, k, k_res, k_rev, k_res_rev)
 
 
 _LOOP_MAX_BATCH = 16
@@ -395,6 +445,6 @@ class FlashHyenaMixer(torch.nn.Module):
         self.in_proj, self.out_proj = in_proj, out_proj
         self.op = FlashHyenaOp(d_model, fft_size, short_filter_weight, short_filter_bias, dtype=dtype, device=device)
 
-    def forward(self, u, k, k_res=None):
-        y = self.op(project_in(self.in_proj.weight, u), k, k_res)
+    def forward(self, u, k, k_res=None, k_rev=None, k_res_rev=None):
+        y = self.op(project_in(self.in_proj.weight, u), k, k_res, k_rev, k_res_rev)
         return project_out(self.out_proj.weight, self.out_proj.bias, y)

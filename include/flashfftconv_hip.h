@@ -39,6 +39,12 @@ double ffc_plan_kf_scale(const ffc_plan* plan);
 /* k (H, Lk) fp32  ->  k_f (H, kf_elems, 2) dtype in internal order, pre-scaled.
  * Replaces torch.fft.fft(k, n=N) + permute + cast (conv.py:572-575, :585, :676 ...). */
 int ffc_kernel_fft(const ffc_plan* plan, const float* k, int64_t H, int64_t Lk, void* kf_out, void* stream);
+/* Bidirectional filter from its two tensors: k (H, Lk) fp32 and k_rev (H, Lr) fp32, both non-null, 0 < Lk, Lr <= fft size N.
+ * Same as ffc_kernel_fft on the row  k_full[h, n] = (n < Lk ? k[h, n] : 0) + (N-1-n < Lr ? k_rev[h, N-1-n] : 0)  (summed in fp32
+ * before rounding): k_rev[m] is the tap at circular lag -(m+1).  Replaces F.pad(k) + F.pad(k_rev.flip(-1)) in front of the
+ * transform (reference examples/bert/monarch_mixer_sequence_mixer_flashfftconv.py:141-170).  Fused sizes (N <= 131072). */
+int ffc_kernel_fft_bi(const ffc_plan* plan, const float* k, int64_t Lk, const float* k_rev, int64_t Lr, int64_t H, void* kf_out,
+                      void* stream);
 /* Same from a natural-order complex64 spectrum (H, N) (e.g. an externally computed FFT). */
 int ffc_kf_pack(const ffc_plan* plan, const void* kf_natural_c64, int64_t H, void* kf_out, void* stream);
 
@@ -151,6 +157,10 @@ int ffc_conv_bwd_kx(const ffc_plan* plan, const void* dout, const void* u, const
 /* dk (H, Lk) fp32 = real(iFFT(sum of partials))[:Lk].  Replaces dk_f_out.sum(0) + un-permute +
  * torch.fft.ifft(..., norm='forward').real[..., :k_len] (conv.py:1758-1761, 1861-1864). */
 int ffc_kernel_ifft_grad(const ffc_plan* plan, const void* ws, int64_t B, int64_t H, int64_t Lk, float* dk, void* stream);
+/* Both gradients of a bidirectional filter (ffc_kernel_fft_bi) from one inverse: dk = dk_full[:, :Lk] and
+ * dk_rev[h, m] = dk_full[h, N-1-m], m < Lr; both non-null fp32. */
+int ffc_kernel_ifft_grad_bi(const ffc_plan* plan, const void* ws, int64_t B, int64_t H, int64_t Lk, float* dk, int64_t Lr,
+                            float* dk_rev, void* stream);
 /* Same from `nslab` caller-owned fp32 slabs [nslab][H][kf_elems][2]: callers that reduce the partial sums themselves
  * (multi-GPU B-shard, flashfftconv/sharding.py: reduce-scatter of dk_f over RCCL, then H/W heads per rank). */
 int ffc_kernel_ifft_grad_slabs(const ffc_plan* plan, const void* slabs, int64_t nslab, int64_t H, int64_t Lk, float* dk,
