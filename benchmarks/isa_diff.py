@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.join(os.path.dirname(HERE), "flash-fft-conv_amd"))
 from isa_view import FLAGS, ROOT            # noqa: E402
-from build import HIP_FLAGS, HIP_SRCS       # noqa: E402
+from build import HIP_FLAGS, HIP_SRCS, UNIT_FLAGS       # noqa: E402
 
 assert FLAGS == HIP_FLAGS, "isa_view.FLAGS is no longer what build.py compiles with: the comparison would not be of the shipped code"
 
@@ -39,12 +39,15 @@ def tree(arg):
 
 
 def command(root, unit):
-    return [HIPCC] + FLAGS + ["--cuda-device-only", "-x", "hip", os.path.join(root, "flash-fft-conv_amd", "csrc", unit)]
+    # (with build.py's per-unit flags: the code of every unit as it ships)
+    return [HIPCC] + FLAGS + UNIT_FLAGS.get(unit, []) + ["--cuda-device-only", "-x", "hip", os.path.join(root, "flash-fft-conv_amd", "csrc", unit)]
 
 
 def cache_path(root, unit):
+    if not os.path.exists(os.path.join(root, "flash-fft-conv_amd", "csrc", unit)):      # a unit that one side does not have: no kernels there
+        return None
     pre = subprocess.run(command(root, unit) + ["-E", "-P", "-o", "-"], check=True, capture_output=True).stdout
-    return os.path.join(CACHE, hashlib.sha256(" ".join(FLAGS).encode() + pre).hexdigest()[:24] + "_" + os.path.splitext(unit)[0] + ".s")
+    return os.path.join(CACHE, hashlib.sha256(" ".join(FLAGS + UNIT_FLAGS.get(unit, [])).encode() + pre).hexdigest()[:24] + "_" + os.path.splitext(unit)[0] + ".s")
 
 
 def compile_to(asm, root, unit):
@@ -56,6 +59,8 @@ def compile_to(asm, root, unit):
 def kernels(asm):
     """{mangled name: normalised lines from its label to its .Lfunc_end label} (a kernel may hold several s_endpgm)."""
     out, name, body = {}, None, []
+    if asm is None:
+        return out
     with open(asm) as fh:
         for line in fh:
             t = line.split(";")[0].rstrip()
@@ -83,7 +88,7 @@ if __name__ == "__main__":
     sides = [(r, u) for r in (a, b) for u in UNITS]
     with ThreadPoolExecutor(max_workers=JOBS) as ex:
         asm = dict(zip(sides, ex.map(lambda ru: cache_path(*ru), sides)))
-        todo = {asm[ru]: ru for ru in sides}                       # one compile per distinct preprocessed text
+        todo = {asm[ru]: ru for ru in sides if asm[ru]}            # one compile per distinct preprocessed text
         list(ex.map(lambda item: compile_to(item[0], *item[1]), sorted(todo.items(), key=lambda item: "ffc_k_" not in item[0])))
     differ = 0
     for u in UNITS:

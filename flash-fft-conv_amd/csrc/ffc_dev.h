@@ -46,7 +46,8 @@ struct DevB {
   using A4 = f32x4;     // 4 consecutive VGPRs: the accumulator tuple of the 16x16x32 MFMA (mfma16)
   static constexpr bool HAS_TR = true;
   // element-wise complex multiply of two accumulator tuples (x (x) t or x (x) conj t): whole-vector fp32 ops,
-  // which gfx950 legalises to v_pk_mul_f32 / v_pk_fma_f32 on aligned register pairs
+  // which gfx950 legalises to v_pk_mul_f32 / v_pk_fma_f32 on aligned register pairs (not in a unit that build.py compiles with packed
+  // fp32 math switched off, UNIT_FLAGS: there the same source becomes one plain VALU instruction per element)
   template <bool CONJ> static FFC_FN void cmul16(A16& re, A16& im, const A16& tr, const A16& ti) {
     const A16 a = re, b = im;
     if (!CONJ) { re = a * tr - b * ti; im = a * ti + b * tr; }
@@ -86,6 +87,7 @@ struct DevB {
                      "a123", "a124", "a125", "a126", "a127");
   }
 #undef FFC_A8
+  static FFC_FN pred nz(u32 a) { return a != 0u; }
   template <int I> static FFC_FN f32 agpr_get() {
     f32 x;
     asm volatile("v_accvgpr_read_b32 %0, a%c1" : "=v"(x) : "n"(I));

@@ -96,6 +96,11 @@ struct DkBiArgs : DkArgs {
   static constexpr bool BI = true;
 };
 
+// live-row form (Modes::dkifft_sp): the slabs of ffc_conv_bwd_sparse, whose dead spectrum rows were never written
+struct DkSpArgs : DkArgs {
+  const float* mask;   // (NT*1024) fp32 0/1 over the bins of one head, k_f's internal order; applied by selection
+};
+
 template <class B, class GEO, int DT>
 struct Modes : Body<B, GEO, DT> {
   using BD = Body<B, GEO, DT>;
@@ -1361,6 +1366,244 @@ struct Modes : Body<B, GEO, DT> {
     }
   }
 
+  // ------------------------------------------------------------------ frequency-sparse fused backward (ffc_conv_bwd_sparse)
+  // k_f is zero outside the spectrum rows k3 < rows / k3 >= 32 - rows (rows <= 4): per tile and lane only FOUR complex values of a
+  // spectrum matter -- accumulator registers 0..3 in lane half 0 (k3 = 0..3), 12..15 in lane half 1 (k3 = 28..31): the "live quad".
+  //   * Z_u: the live quad of each of the wave's four tiles stays in registers as packed dtype pairs (one U4 per tile, rounded exactly
+  //     as the dense kernel's scratch copy is): no spectrum scratch in global memory, no round trip between the two transforms of a pair
+  //   * dk_f: W += Z_d conj(Z_u) on the live quad, 8 sums per tile (W[8 T + 4 part + q]) instead of 32.  32 sums per wave need no
+  //     hand-addressed accumulation registers: the kernel reserves none, the whole 256-register file of a wave is architectural, and the
+  //     transforms run both tiles of a pair of tiles in lock-step (as the sparse forward does); the inner twiddle table is streamed from LDS
+  //   * du and, gated, the forward output for dpostgate: (x) conj(k_f) / k_f on the live rows (Body::kf_mul_sp), then the inverse with
+  //     the one-K-step first stage on PlanTabs::mat_sp, held in registers for both
+  //   * the slab receives the live quads only: spectrum rows rho = 0 (lane half 0) and rho = 7 (lane half 1) of every tile; the rest
+  //     of the slab is never written (dkifft_sp never reads it)
+  static FFC_FN pred sp_up() { return (B::opaque(B::lane()) >> 5) >= 1; }
+  static FFC_FN f32 sp_live(pred up, const A16& x, int q) { return B::as_f32(B::sel(up, B::as_u32(x[12 + q]), B::as_u32(x[q]))); }
+  // forward half of two tiles in lock-step (the first half of Body::inner_tile2_sp)
+  // TWR: the inner twiddle table is resident in R.tw; else streamed from LDS (the backward's pair loop carries the sums and Z_u instead)
+  template <bool TWR>
+  static FFC_FN void sp_tw(A16& re, A16& im, const InnerRegs& R, bool conj) {
+    if constexpr (TWR) { if (conj) BD::cmul_conj(re, im, R.tw); else BD::cmul(re, im, R.tw); }
+    else { if (conj) BD::template cmul_lds<true>(re, im, GEO::L_TW); else BD::template cmul_lds<false>(re, im, GEO::L_TW); }
+  }
+  template <bool TWR>
+  static FFC_FN void sp_fwd2(int tauA, const InnerRegs& R, Unit un, A16& reA, A16& imA, A16& reB, A16& imB) {
+    Op opA, opB;
+    BD::load_tile_op(tauA, opA, un, R);
+    BD::load_tile_op(tauA + 1, opB, un, R);
+    reA = B::a16_zero(); imA = B::a16_zero();
+    BD::template cmm<false, true>(reA, imA, opA, R.F2);
+    reB = B::a16_zero(); imB = B::a16_zero();
+    BD::template cmm<false, true>(reB, imB, opB, R.F2);
+    sp_tw<TWR>(reA, imA, R, false); BD::to_op(reA, imA, opA);
+    reA = B::a16_zero(); imA = B::a16_zero();
+    BD::template cmm<false, false>(reA, imA, opA, R.F2);
+    sp_tw<TWR>(reB, imB, R, false); BD::to_op(reB, imB, opB);
+    reB = B::a16_zero(); imB = B::a16_zero();
+    BD::template cmm<false, false>(reB, imB, opB, R.F2);
+  }
+  // inverse half of two tiles whose live rows hold the spectrum (the second half of Body::inner_tile2_sp), back into E
+  template <bool TWR>
+  static FFC_FN void sp_inv2(float s_inv, int tauA, const InnerRegs& R, const typename BD::Mat& Fs, A16& reA, A16& imA, A16& reB, A16& imB) {
+    Op opA, opB;
+    BD::to_op_sp(reA, imA, opA);
+    reA = B::a16_zero(); imA = B::a16_zero();
+    BD::template cmm<true, true>(reA, imA, opA, Fs, 1);
+    BD::to_op_sp(reB, imB, opB);
+    reB = B::a16_zero(); imB = B::a16_zero();
+    BD::template cmm<true, true>(reB, imB, opB, Fs, 1);
+    sp_tw<TWR>(reA, imA, R, true); BD::to_op(reA, imA, opA);
+    reA = B::a16_zero(); imA = B::a16_zero();
+    BD::template cmm<true, true>(reA, imA, opA, R.F2);
+    sp_tw<TWR>(reB, imB, R, true); BD::to_op(reB, imB, opB);
+    reB = B::a16_zero(); imB = B::a16_zero();
+    BD::template cmm<true, true>(reB, imB, opB, R.F2);
+    BD::template oi_twiddle<false>(s_inv, tauA, reA, imA);
+    BD::tile_store(tauA, R, reA, imA);
+    BD::template oi_twiddle<false>(s_inv, tauA + 1, reB, imB);
+    BD::tile_store(tauA + 1, R, reB, imB);
+  }
+  // the live quad as (re, im) dtype pairs
+  static FFC_FN U4 sp_pack_live(const A16& re, const A16& im) {
+    const pred up = sp_up();
+    U4 z;
+    z.x = B::sel(up, B::template pack<DT>(re[12], im[12]), B::template pack<DT>(re[0], im[0]));
+    z.y = B::sel(up, B::template pack<DT>(re[13], im[13]), B::template pack<DT>(re[1], im[1]));
+    z.z = B::sel(up, B::template pack<DT>(re[14], im[14]), B::template pack<DT>(re[2], im[2]));
+    z.w = B::sel(up, B::template pack<DT>(re[15], im[15]), B::template pack<DT>(re[3], im[3]));
+    return z;
+  }
+  // first transform of a pair, tiles T0 and T0 + 1 of the wave: Z_u's live quads into zu; WITH_Y: iFFT(Z_u k_f) back into E (dpostgate)
+  template <int T0>
+  static FFC_FN void sp_tiles_u(const ConvArgs& a, int h, Unit un, const InnerRegs& R, const typename BD::Mat& Fs, U4 (&zu)[GEO::TPW], bool with_y) {
+    const int tauA = un.wq * GEO::TPW + T0;
+    typename BD::KfRegsSp kfA, kfB;
+    if (with_y) { BD::load_kf_sp(a, h, tauA, kfA); BD::load_kf_sp(a, h, tauA + 1, kfB); }
+    A16 reA, imA, reB, imB;
+    sp_fwd2<false>(tauA, R, un, reA, imA, reB, imB);
+    zu[T0] = sp_pack_live(reA, imA);
+    zu[T0 + 1] = sp_pack_live(reB, imB);
+    if (with_y) {
+      BD::kf_mul_sp(a, kfA, reA, imA);
+      BD::kf_mul_sp(a, kfB, reB, imB);
+      sp_inv2<false>(a.s_inv, tauA, R, Fs, reA, imA, reB, imB);
+    }
+  }
+  // W_T += Z_d conj(Z_u) on the live quad: W[8 T + 4 part + q]
+  template <int T>
+  static FFC_FN void sp_w_acc(f32 (&W)[8 * GEO::TPW], const U4& z, const A16& re, const A16& im) {
+    const pred up = sp_up();
+    const u32 zq[4] = {z.x, z.y, z.z, z.w};
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const f32 zr = B::template unpack_lo<DT>(zq[q]), zi = B::template unpack_hi<DT>(zq[q]);
+      const f32 dr = sp_live(up, re, q), di = sp_live(up, im, q);
+      W[8 * T + q] = W[8 * T + q] + (dr * zr + di * zi);
+      W[8 * T + 4 + q] = W[8 * T + 4 + q] + (di * zr - dr * zi);
+    }
+  }
+  // second transform of a pair: Z_d, the dk_f sums, iFFT(Z_d conj(k_f)) back into E.  `ac`: ConvArgs with conj_kf = 1
+  template <int T0>
+  static FFC_FN void sp_tiles_d(const ConvArgs& ac, int h, Unit un, const InnerRegs& R, const typename BD::Mat& Fs, const U4 (&zu)[GEO::TPW],
+                                 f32 (&W)[8 * GEO::TPW]) {
+    const int tauA = un.wq * GEO::TPW + T0;
+    typename BD::KfRegsSp kfA, kfB;
+    BD::load_kf_sp(ac, h, tauA, kfA);
+    BD::load_kf_sp(ac, h, tauA + 1, kfB);
+    A16 reA, imA, reB, imB;
+    sp_fwd2<false>(tauA, R, un, reA, imA, reB, imB);
+    sp_w_acc<T0>(W, zu[T0], reA, imA);
+    sp_w_acc<T0 + 1>(W, zu[T0 + 1], reB, imB);
+    BD::kf_mul_sp(ac, kfA, reA, imA);
+    BD::kf_mul_sp(ac, kfB, reB, imB);
+    sp_inv2<false>(ac.s_inv, tauA, R, Fs, reA, imA, reB, imB);
+  }
+  // the live quad of one tile's sums into the slab: spectrum row rho = 0 (lane half 0, k3 = 0..3) or 7 (lane half 1, k3 = 28..31)
+  static FFC_FN void sp_w_store(float* slab, int tau, i32 lane, const f32* w) {
+    const i32 c = lane & 31, hi = lane >> 5;
+    const i32 idx = ((hi * 7 + tau * 8) * 32 + c) * 2;
+    U4 n0, n1;
+    n0.x = B::as_u32(w[0]); n0.y = B::as_u32(w[4]); n0.z = B::as_u32(w[1]); n0.w = B::as_u32(w[5]);
+    n1.x = B::as_u32(w[2]); n1.y = B::as_u32(w[6]); n1.z = B::as_u32(w[3]); n1.w = B::as_u32(w[7]);
+    B::g_w128(slab, idx, n0, B::ptrue());
+    B::g_w128(slab, idx + 1, n1, B::ptrue());
+  }
+  // end of a chunk: the live quads of the wave's tiles into the chunk's slab.  UPW > 1 (fft 16384: the workgroup's units are pairs of the
+  // same head): every wave parks its 32 sums in the idle exchange buffers, unit 0's waves add the units up in a fixed order.
+  static FFC_FN void sp_w_finish(float* slab, int u, Unit un, const f32 (&W)[8 * GEO::TPW]) {
+    const i32 lane = B::opaque(B::lane());
+    const int tau0 = un.wq * GEO::TPW;
+    if constexpr (GEO::UPW == 1) {
+#pragma unroll
+      for (int t = 0; t < GEO::TPW; t++) sp_w_store(slab, tau0 + t, lane, &W[8 * t]);
+    } else {
+      static_assert(GEO::UPW * GEO::NW * 8192 <= GEO::UPW * GEO::EBYTES, "parking area fits the exchange buffers");
+      B::barrier();              // every unit's last output rows have left the exchange buffers
+#pragma unroll
+      for (int j = 0; j < 8 * GEO::TPW; j++) B::lds_w32(lane * 4 + (GEO::L_E + (u * GEO::NW + un.wq) * 8192 + j * 256), B::as_u32(W[j]));
+      B::barrier();
+      if (u == 0) {
+#pragma unroll
+        for (int t = 0; t < GEO::TPW; t++) {
+          f32 s[8];
+#pragma unroll
+          for (int j = 0; j < 8; j++) {
+            s[j] = B::fconst(0.f);
+#pragma unroll
+            for (int s2 = 0; s2 < GEO::UPW; s2++)
+              s[j] = s[j] + B::as_f32(B::lds_r32(lane * 4 + (GEO::L_E + (s2 * GEO::NW + un.wq) * 8192 + (8 * t + j) * 256)));
+          }
+          sp_w_store(slab, tau0 + t, lane, s);
+        }
+      }
+    }
+  }
+  // The recomputing fused backward of a frequency-sparse module: per pair FFT(u pregate) [+ dpostgate], FFT(dout postgate), dk_f sums,
+  // du (+ dpregate) -- the dense form is Modes::bwd.  d.c.conj_kf must be 0; d.zscratch, d.zin, d.yraw and the dk tail are not used.
+  template <bool HALF>
+  static FFC_FN void bwd_sp(const DkfArgs& d, int h, int chunk) {
+    static_assert(GEO::HAS_SP && GEO::TPW == 4, "sparse phase B: 32-point inner digits, four tiles per wave");
+    const ConvArgs& a = d.c;
+    constexpr int NCX = HALF ? BD::NCH / 2 : BD::NCH;
+    BD::setup_tables(a.tab, a.t);
+    const int wv = B::wave();
+    Unit un;
+    un.wq = wv % GEO::NW;
+    const int u = wv / GEO::NW;
+    un.eb = u * GEO::EBYTES;
+    const int p0 = chunk * a.ppc;
+    int p1 = p0 + a.ppc;
+    if (p1 > a.npair) p1 = a.npair;
+    ConvArgs ac = a;            // (x) conj(k_f)
+    ac.conj_kf = 1;
+    ConvArgs ad = a;            // dc = dout * postgate
+    ad.u = d.dout; ad.pregate = a.postgate; ad.sbu = d.sbd; ad.sbg = a.sbp;
+    ConvArgs ao = a;            // du = dv * pregate
+    ao.y = d.du; ao.postgate = a.pregate; ao.sby = d.sbdu; ao.sbp = a.sbg;
+    ConvArgs ap = a;            // dpre = dv * u
+    ap.y = d.dpre; ap.postgate = a.u; ap.sby = d.sbdpre; ap.sbp = a.sbu;
+    ConvArgs aq = a;            // dpost = conv(u*pregate, k) * dout
+    aq.y = d.dpost; aq.postgate = d.dout; aq.sby = d.sbdpost; aq.sbp = d.sbd;
+    const bool with_y = d.dpost != nullptr;
+    float* slab = d.ws + ((int64_t)chunk * a.H + h) * (GEO::NT * 2048);
+    f32 W[8 * GEO::TPW];      // the dk_f sums of the wave's four live quads: architectural registers, carried over the pair loop
+#pragma unroll
+    for (int j = 0; j < 8 * GEO::TPW; j++) W[j] = B::fconst(0.f);
+    const int iters = (p1 - p0 + GEO::UPW - 1) / GEO::UPW;
+#pragma unroll 1
+    for (int it = 0; it < iters; it++) {
+      const int p = p0 + it * GEO::UPW + u;
+      const bool act = p < p1;
+      U4 zu[GEO::TPW];
+#pragma unroll
+      for (int t = 0; t < GEO::TPW; t++) { zu[t].x = B::uconst(0); zu[t].y = B::uconst(0); zu[t].z = B::uconst(0); zu[t].w = B::uconst(0); }
+      if (act) {
+        BD::template rows_in_sel<NCX, false>(a, h, p, un);
+        B::lds_fence();
+        BD::template outer_stage<true, HALF>(a.L, un, a.s_fwd);
+      }
+      BD::unit_barrier();
+      if (act) {
+        InnerRegs R;
+        BD::template load_inner<false>(R, un);
+        typename BD::Mat Fs;
+        BD::lds_mat_sp(Fs);
+        sp_tiles_u<0>(a, h, un, R, Fs, zu, with_y);
+        sp_tiles_u<2>(a, h, un, R, Fs, zu, with_y);
+      }
+      BD::unit_barrier();
+      if (act) {
+        if (with_y) {
+          BD::template outer_stage<false, HALF>(a.L, un, 1.0f, Pass(), a.flags);
+          B::lds_fence();
+          BD::template rows_out<NCX>(aq, h, p, un);
+        }
+        // (no barrier: phase C, rows_out, rows_in and phase A stay inside the wave's own column slice of E)
+        BD::template rows_in_sel<NCX, false>(ad, h, p, un);
+        B::lds_fence();
+        BD::template outer_stage<true, HALF>(a.L, un, a.s_fwd);
+      }
+      BD::unit_barrier();
+      if (act) {
+        InnerRegs R;
+        BD::template load_inner<false>(R, un);
+        typename BD::Mat Fs;
+        BD::lds_mat_sp(Fs);
+        sp_tiles_d<0>(ac, h, un, R, Fs, zu, W);
+        sp_tiles_d<2>(ac, h, un, R, Fs, zu, W);
+      }
+      BD::unit_barrier();
+      if (act) {
+        BD::template outer_stage<false, HALF>(a.L, un, 1.0f, Pass(), a.flags);
+        B::lds_fence();
+        BD::template rows_out<NCX>(ao, h, p, un);
+        if (d.dpre) BD::template rows_out<NCX>(ap, h, p, un);
+      }
+    }
+    sp_w_finish(slab, u, un, W);
+  }
+
   // W += Zd * conj(Zv) (Zv as packed dtype pairs)
   static FFC_FN void w_add(A16& wre, A16& wim, const ZReg& zv, const A16& re, const A16& im) {
 #pragma unroll
@@ -1584,6 +1827,69 @@ struct Modes : Body<B, GEO, DT> {
         }
         if constexpr (KA::BI) fstore8_rev(a.dkr, hd * a.Lr, (GEO::N * ps.R - 8) - n, a.Lr, a.fast != 0, ok, ps.k0 > 0, vr);
       }
+    }
+  }
+  // dk_f -> dk from the live rows alone (slabs of Modes::bwd_sp): per tile and lane the live quad is summed over the slabs, every
+  // other bin of the tile is zero, and a bin the mask drops is replaced by zero (a select: the slab may hold anything there).  The
+  // inverse starts with the one-K-step stage on PlanTabs::mat_sp, two tiles in lock-step.
+  static FFC_FN void w_load_sp(const DkSpArgs& a, int unit_id, int tau, A16& re, A16& im) {
+    const i32 lane = B::opaque(B::lane());
+    const i32 c = lane & 31, hi = lane >> 5;
+    const pred up = hi >= 1;
+    const int64_t slab_stride = (int64_t)a.H * (GEO::NT * 2048);   // floats
+    const i32 row = (hi * 7 + tau * 8) * 32 + c;                    // spectrum row rho = 0 / 7 of the tile, 4 complex values per lane
+    const U4 m = B::g_r128(a.mask, row);
+    f32 sr[4], si[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { sr[q] = B::fconst(0.f); si[q] = B::fconst(0.f); }
+#pragma unroll 1
+    for (int s = 0; s < a.nslab; s++) {
+      const float* sl = a.ws + s * slab_stride;
+      const i32 idx = row * 2 + unit_id * (GEO::NT * 512);
+      U4 o0 = B::g_r128(sl, idx), o1 = B::g_r128(sl, idx + 1);
+      sr[0] = sr[0] + B::as_f32(o0.x); si[0] = si[0] + B::as_f32(o0.y); sr[1] = sr[1] + B::as_f32(o0.z); si[1] = si[1] + B::as_f32(o0.w);
+      sr[2] = sr[2] + B::as_f32(o1.x); si[2] = si[2] + B::as_f32(o1.y); sr[3] = sr[3] + B::as_f32(o1.z); si[3] = si[3] + B::as_f32(o1.w);
+    }
+    const u32 mq[4] = {m.x, m.y, m.z, m.w};
+    const u32 zero = B::uconst(0);
+    re = B::a16_zero(); im = B::a16_zero();
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const pred keep = B::nz(mq[q]);
+      const u32 vr = B::sel(keep, B::as_u32(sr[q] * a.scale), zero), vi = B::sel(keep, B::as_u32(si[q] * a.scale), zero);
+      re[q] = B::as_f32(B::sel(up, zero, vr)); im[q] = B::as_f32(B::sel(up, zero, vi));
+      re[12 + q] = B::as_f32(B::sel(up, vr, zero)); im[12 + q] = B::as_f32(B::sel(up, vi, zero));
+    }
+  }
+  static FFC_FN void dkifft_sp(const DkSpArgs& a, int wg) {
+    static_assert(GEO::HAS_SP && GEO::TPW == 4, "live-row dk inverse: 32-point inner digits");
+    BD::setup_tables(a.tab, a.t);
+    const int wv = B::wave();
+    Unit un;
+    un.wq = wv % GEO::NW;
+    const int u = wv / GEO::NW;
+    un.eb = u * GEO::EBYTES;
+    const int unit_id = wg * GEO::UPW + u;
+    const bool act = unit_id < a.H;
+    if (act) {
+      InnerRegs R;
+      BD::load_inner(R, un);
+      typename BD::Mat Fs;
+      BD::lds_mat_sp(Fs);
+#pragma unroll 1
+      for (int tt = 0; tt < GEO::TPW; tt += 2) {
+        const int tau = un.wq * GEO::TPW + tt;
+        A16 reA, imA, reB, imB;
+        w_load_sp(a, unit_id, tau, reA, imA);
+        w_load_sp(a, unit_id, tau + 1, reB, imB);
+        sp_inv2<true>(a.s_inv, tau, R, Fs, reA, imA, reB, imB);
+      }
+    }
+    B::barrier();
+    if (act) {
+      BD::template outer_stage<false, false>(live_len(a, GEO::N), un);
+      B::lds_fence();
+      dk_rows_out(a, unit_id, un);
     }
   }
   template <class KA>

@@ -155,6 +155,28 @@ inline BwdRoute bwd_route(const DkfArgs& d, bool dkf) {
   return r;
 }
 
+// ---- frequency-sparse fused backward (bwd_sp_kernel, Modes::bwd_sp) and its dk_f -> dk kernel (dkifft_sp_kernel): refused where the
+// forward's sparse form is (fwd_route: GEO::HAS_SP, single pass, 1 <= rows <= 4, no spectrum buffer); one workgroup per (head, chunk)
+struct BwdSpRoute {
+  bool half;
+  int grid, lds_max, lds;
+  const char* err;
+};
+static constexpr const char* NO_SPARSE_BWD = "frequency-sparse backward: fft 16384 / 32768, 1 <= rows <= 4, no spectrum buffer";
+template <class GEO>
+inline BwdSpRoute bwd_sp_route(const DkfArgs& d, int rows) {
+  const ConvArgs& c = d.c;
+  BwdSpRoute r{};
+  if (!GEO::HAS_SP || c.R > 1 || rows < 1 || rows > 4 || d.zin || d.yraw) { r.err = NO_SPARSE_BWD; return r; }
+  r.grid = ((c.H + 7) & ~7) * c.nchunk;
+  r.lds_max = r.lds = GEO::LDS_BYTES;
+  r.half = (GEO::N1 / 2) * GEO::Mi >= c.L;
+  return r;
+}
+// workgroups of the live-row dk inverse: UPW heads each
+template <class GEO>
+inline int dk_sp_grid(int H) { return (H + GEO::UPW - 1) / GEO::UPW; }
+
 // ---- steps a convolution launch may take over from a launch of their own (flags: the plan's tuning flags, FFC_FLAGS)
 // k -> k_f inside the forward launch (Modes::kfft_head): a workgroup owns its head, fft 8192 / 16384 / 32768 (the sizes whose waves
 // meet at workgroup barriers anyway); tuning flag 64 keeps the separate launch

@@ -104,6 +104,7 @@ struct SimB {
     wi.y = wi.y + (b[r0 + 1] * zr.y - a[r0 + 1] * zi.y);
   }
   static void agpr_reserve() {}
+  static pred nz(const u32& a) { pred r; for (int i = 0; i < 64; i++) r.v[i] = a.v[i] != 0u; return r; }
   template <int I> static f32 agpr_get() { return g_agpr[I]; }
   template <int I> static void agpr_set(const f32& x) { g_agpr[I] = x; }
   static void pin(W4&) {}
@@ -522,6 +523,30 @@ template <class GEO, int DT> struct DkBiRun {
     for (int wg = 0; wg < (nunits + GEO::UPW - 1) / GEO::UPW; wg++)
       run_wg(GEO::WGW, sim_lds<GEO>(), [&]() { Modes<SimB, GEO, DT>::dkifft(a, wg); });
     return 0;
+  }
+};
+// the frequency-sparse backward pair (Modes::bwd_sp / dkifft_sp), by the library's rule (ffc::bwd_sp_route)
+template <class GEO, int DT> struct BwdSpRun {
+  static int run(const DkfArgs& d, int rows) {
+    const BwdSpRoute r = bwd_sp_route<GEO>(d, rows);
+    if (r.err) return NO_KERNEL;
+    if constexpr (GEO::HAS_SP) {
+      return pick([&](auto half) -> int {
+        return sim_jobs(d.c.H, d.c.nchunk, r.lds, [&](int h, int c) { Modes<SimBO, GEO, DT>::template bwd_sp<decltype(half)::value>(d, h, c); });
+      }, r.half);
+    } else {
+      return NO_KERNEL;
+    }
+  }
+};
+template <class GEO, int DT> struct DkSpRun {
+  static int run(const DkSpArgs& a) {
+    if constexpr (GEO::HAS_SP) {
+      for (int wg = 0; wg < dk_sp_grid<GEO>(a.H); wg++) run_wg(GEO::WGW, GEO::LDS_BYTES, [&]() { Modes<SimB, GEO, DT>::dkifft_sp(a, wg); });
+      return 0;
+    } else {
+      return NO_KERNEL;
+    }
   }
 };
 template <class GEO, int DT> struct UpwGet { static int run(int* out) { *out = GEO::UPW; return 0; } };
@@ -980,6 +1005,41 @@ int ffcsim_conv_bwd(int N, int dtype, const void* dout, const void* u, const voi
   d.zscratch = zs.data();
   int rc = dispatch<BwdRun>(N, dtype, d);
   return rc < 0 ? rc : a.nchunk;
+}
+
+// frequency-sparse fused backward (ffc_conv_bwd_sparse, Modes::bwd_sp): du, dpre / dpost (nullable) and the live rows of the dk_f slabs;
+// returns the number of slabs, NO_KERNEL where the library refuses the call (ffc::bwd_sp_route)
+int ffcsim_conv_bwd_sparse(int N, int dtype, const void* dout, const void* u, const void* kf, const void* pregate, const void* postgate,
+                           void* du, void* dpre, void* dpost, float* ws, int B, int H, int L, int nchunk, int rows) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  DkfArgs d{};
+  ConvArgs& a = d.c;
+  a.u = u; a.kf = kf; a.pregate = pregate; a.postgate = postgate; a.tab = p.blob.data(); a.t = p.tabs;
+  a.B = B; a.H = H; a.L = L; a.npair = (B + 1) / 2; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
+  a.sbu = a.sbg = a.sbp = a.sby = (int64_t)H * L; d.sbd = d.sbdu = d.sbdpre = d.sbdpost = (int64_t)H * L;
+  const int upw = ffcsim_upw(N);
+  const int iters_total = (a.npair + upw - 1) / upw;
+  if (nchunk > iters_total) nchunk = iters_total;
+  a.ppc = ((iters_total + nchunk - 1) / nchunk) * upw; a.nchunk = (a.npair + a.ppc - 1) / a.ppc;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R; a.flags = g_sim_flags; a.sparse = rows;
+  d.dout = dout; d.ws = ws; d.du = du; d.dpre = dpre; d.dpost = dpost;
+  const int rc = dispatch<BwdSpRun>(N, dtype, d, rows);
+  return rc < 0 ? rc : a.nchunk;
+}
+// dk from the live rows of those slabs (ffc_kernel_ifft_grad_sp, Modes::dkifft_sp); bf16 arithmetic, as ffcsim_kernel_ifft_grad
+// (dtype: the plan that wrote the slabs -- its forward scale is what W carries)
+int ffcsim_kernel_ifft_grad_sp(int N, int dtype, const float* ws, const float* mask, int rows, int nslab, int H, int Lk, float* dk) {
+  HostPlan p, pd;
+  if (!build_plan(N, DT_BF16, &p) || !build_plan(N, dtype, &pd)) return -1;
+  if (rows < 1 || rows > 4 || p.R > 1) return NO_KERNEL;
+  DkSpArgs a{};
+  a.ws = ws; a.dk = dk; a.tab = p.blob.data(); a.t = p.tabs; a.H = H; a.Lk = Lk; a.nslab = nslab;
+  a.scale = (float)(1.0 / pd.s_fwd); a.s_inv = (float)p.s_inv;
+  a.fast = (Lk % 4 == 0) && !g_force_slow;
+  a.R = 1; a.mask = mask;
+  return dispatch<DkSpRun>(N, DT_BF16, a);
 }
 
 int ffcsim_kernel_ifft_grad_c(int N, const float* ws, int nslab, int H, void* outpair, float scale) {

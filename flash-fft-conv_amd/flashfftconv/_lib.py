@@ -47,6 +47,8 @@ def lib():
         L.ffc_conv_bwd_dkf.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd_gated.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
+        L.ffc_conv_bwd_sparse.argtypes = [c_vp] * 11 + [c_i64, c_i64, c_i64, c_int, c_vp]
+        L.ffc_kernel_ifft_grad_sp.argtypes = [c_vp, c_vp, c_vp, c_int, c_i64, c_i64, c_i64, c_vp, c_vp]
         L.ffc_kernel_ifft_grad.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]
         L.ffc_kernel_ifft_grad_bi.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp]
         L.ffc_kernel_ifft_grad_slabs.argtypes = [c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp]

@@ -129,7 +129,8 @@ def get_plan(seqlen, dtype, device):
 
 def reload_env():
     """tuning scripts: re-read FFC_* environment knobs into every cached plan (launches never read the environment)"""
-    global _ONE_LAUNCH_LEVEL
+    global _ONE_LAUNCH_LEVEL, _SPARSE_BWD
+    _SPARSE_BWD = _os.environ.get("FFC_SPARSE_BWD", "1") != "0"
     for p in list(_PLANS.values()):
         _lib.lib().ffc_plan_reload_env(p.handle)
         p.__dict__.pop("_ws_cache", None)      # the workspace size depends on FFC_WG_MULT (chunks per head): ADVICE r04
@@ -171,6 +172,26 @@ def _conv_sparse(plan, u, kf, pregate, postgate, conj, rows):
     _lib.check(_lib.lib().ffc_conv_fwd_sparse(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
                                               _lib.ptr(y), B, H, L, int(conj), rows, _lib.stream_ptr()), "ffc_conv_fwd_sparse")
     return y
+
+
+# FFC_SPARSE_BWD=0 (read by reload_env): the dense recomputing backward + torch mask on the frequency-sparse route, for A/B runs
+_SPARSE_BWD = _os.environ.get("FFC_SPARSE_BWD", "1") != "0"
+
+
+def _bwd_sparse(plan, dout, u, kf, pregate, postgate, rows, ws, du, dpre, dpost):
+    """fused backward of the compute-skipping route (ffc_conv_bwd_sparse): du / dpre / dpost and the LIVE rows of the dk_f slabs in ws"""
+    B, H, L = u.shape
+    _lib.check(_lib.lib().ffc_conv_bwd_sparse(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
+                                              _lib.ptr(du), _lib.ptr(dpre), _lib.ptr(dpost), _lib.ptr(ws), None, B, H, L, rows,
+                                              _lib.stream_ptr()), "ffc_conv_bwd_sparse")
+
+
+def _ifft_grad_sparse(plan, ws, mask, rows, B, H, k_len, device):
+    """dk from those slabs: live rows only, the module's bin mask applied by selection (ffc_kernel_ifft_grad_sp)"""
+    dk = torch.empty(H, k_len, dtype=torch.float32, device=device)
+    _lib.check(_lib.lib().ffc_kernel_ifft_grad_sp(plan.handle, _lib.ptr(ws), _lib.ptr(mask), rows, B, H, k_len, _lib.ptr(dk),
+                                                  _lib.stream_ptr()), "ffc_kernel_ifft_grad_sp")
+    return dk
 
 
 # Memory budget of the kept spectra (ADVICE r03): save_spectrum spends memory the reference does not (2x the bytes of u per
@@ -771,6 +792,7 @@ class _FlashFFTConvFn(torch.autograd.Function):
             # module.save_spectrum = False (or FFC_SAVE_SPECTRUM=0) keeps the reference's recomputing backward.
             z = yraw = None
             rows = 0 if one_call else _sparse_rows(mod, plan)      # low-pass k_f: the forward kernel that skips the all-zero spectrum rows
+            ctx.sparse_rows = rows      # the backward takes the live-row kernels exactly where this call took _conv_sparse
             if rows:
                 out = _conv_sparse(plan, u, kf, pregate, postgate, False, rows)
             elif mod.training and mod.save_spectrum and _recording() and any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4)):
@@ -858,6 +880,13 @@ class _FlashFFTConvFn(torch.autograd.Function):
                                           k_len, B, H, L, _lib.stream_ptr()), "ffc_conv_bwd_k")
             if dk.dtype != ctx.k_dtype:
                 dk = dk.to(ctx.k_dtype)
+            return (du, dk, None, dpre, dpost) if ctx.gated else (du, dk, None, None, None)
+        rows = getattr(ctx, "sparse_rows", 0) if _SPARSE_BWD else 0
+        if rows:
+            # frequency-sparse route: the recomputing kernel on the live spectrum rows, then dk_f -> dk on the live rows with the bin
+            # mask applied by selection (no full slabs written, no torch pass over them)
+            _bwd_sparse(plan, dout, u, kf, pregate, postgate, rows, ws, du, dpre, dpost)
+            dk = _ifft_grad_sparse(plan, ws, ctx.mod._kf_mask(plan, torch.float32), rows, B, H, k_len, u.device).to(ctx.k_dtype)
             return (du, dk, None, dpre, dpost) if ctx.gated else (du, dk, None, None, None)
         if (z is not None or yraw is not None) and ctx.gated:
             # dpostgate = dout * y_raw out of the kernel's dout row load (round 3: a torch elementwise kernel, 3 x |u| bytes more)

@@ -90,6 +90,20 @@ int ffc_conv_bwd(const ffc_plan* plan, const void* dout, const void* u, const vo
 int ffc_conv_bwd_gated(const ffc_plan* plan, const void* dout, const void* u, const void* kf, const void* pregate,
                        const void* postgate, void* du, void* dpre, void* dpost, void* ws, int64_t B, int64_t H, int64_t L,
                        void* stream);
+/* ffc_conv_bwd_gated for the LOW-PASS k_f that ffc_conv_fwd_sparse takes (rows as there, 1 .. 4; fft 16384 / 32768): the recomputing
+ * kernel on the live spectrum rows only.  Same du / dpre / dpost; of the fp32 dk_f slabs in ws ONLY the live rows are written (the
+ * others keep whatever ws held): finish with ffc_kernel_ifft_grad_sp.  rows only validates the call: the kernels always work on the
+ * four rows per side that rows <= 4 allows (rows = 1 costs what rows = 4 costs); what lies outside the kept bins is zero in k_f and
+ * dropped by the mask of ffc_kernel_ifft_grad_sp.  zin: must be null (no saved-spectra form); any other fft
+ * size, rows outside 1 .. 4 or a spectrum buffer return non-zero without a launch. */
+int ffc_conv_bwd_sparse(const ffc_plan* plan, const void* dout, const void* u, const void* kf, const void* pregate,
+                        const void* postgate, void* du, void* dpre, void* dpost, void* ws, const void* zin, int64_t B, int64_t H,
+                        int64_t L, int rows, void* stream);
+/* dk (H, Lk) fp32 from the slabs of ffc_conv_bwd_sparse (same B, H, rows): reads the live rows only, takes every other bin as zero
+ * and keeps a live-row bin where mask (kf_elems fp32, 0 / 1, k_f's internal order, 16-byte aligned) is non-zero -- by selection, so
+ * what the slabs hold elsewhere, NaN included, never reaches dk. */
+int ffc_kernel_ifft_grad_sp(const ffc_plan* plan, const void* ws, const float* mask, int rows, int64_t B, int64_t H, int64_t Lk,
+                            float* dk, void* stream);
 int ffc_conv_bwd_gated_strided(const ffc_plan* plan, const void* dout, const void* u, const void* kf, const void* pregate,
                                const void* postgate, void* du, void* dpre, void* dpost, void* ws, int64_t B, int64_t H,
                                int64_t L, int64_t sb_dout, int64_t sb_u, int64_t sb_pre, int64_t sb_post, int64_t sb_du,
