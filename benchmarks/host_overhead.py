@@ -1,10 +1,16 @@
 """Host-side cost of one module call: a shape so small that the GPU is never the bottleneck (fft 256, B=2, H=4), many calls,
-wall time per call + the cProfile split.  usage: host_overhead.py [profile]"""
-import cProfile, os, pstats, sys, time
+wall time per call + the cProfile split; the same for the fused Hyena operator at its host-bound shape (fft 256, B=2, D=8).
+usage: host_overhead.py [--pkg DIR] [profile]    --pkg: the directory that holds the `flashfftconv` package to import (A/B runs of two
+versions of the Python side on one library, FFC_LIB)"""
+import argparse, cProfile, os, pstats, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path[:0] = [os.path.join(ROOT, "flash-fft-conv_amd"), ROOT]
+ap = argparse.ArgumentParser()
+ap.add_argument("--pkg", default=os.path.join(ROOT, "flash-fft-conv_amd"))
+ap.add_argument("profile", nargs="?")
+args = ap.parse_args()
+sys.path[:0] = [os.path.abspath(args.pkg), ROOT]
 import torch
-from flashfftconv import FlashFFTConv
+from flashfftconv import FlashFFTConv, FlashHyenaOp
 
 N, B, H = 256, 2, 4
 L = N // 2
@@ -41,14 +47,26 @@ def step_gated():
     mod(u, k, *g).backward(dout)
 
 
+DH = 8
+hy = FlashHyenaOp(DH, N, torch.randn(3 * DH, 1, 3), torch.randn(3 * DH), dtype=torch.bfloat16, device="cuda").cuda()
+x3 = torch.randn(B, 3 * DH, L, device="cuda").bfloat16().requires_grad_(True)
+kh = torch.randn(DH, L, device="cuda").requires_grad_(True)
+dy = torch.randn(B, DH, L, device="cuda").bfloat16()
+
+
+def hyena_step():
+    x3.grad = None; kh.grad = None
+    hy(x3, kh).backward(dy)
+
+
 def torch_ref():       # the torch.fft form of the same op, for scale
     with torch.no_grad():
         torch.fft.irfft(torch.fft.rfft(u.float(), n=N) * torch.fft.rfft(k, n=N), n=N)[..., :L]
 
 
-for f in (fwd_infer, fwd_train, fwd_train_gated, step, step_gated, torch_ref):
+for f in (fwd_infer, fwd_train, fwd_train_gated, step, step_gated, hyena_step, torch_ref):
     print(f"{f.__name__:18s} {wall(f):7.1f} us per call", flush=True)
-if len(sys.argv) > 1:
+if args.profile:
     pr = cProfile.Profile(); pr.enable()
     for _ in range(2000): step()
     torch.cuda.synchronize(); pr.disable()

@@ -15,6 +15,8 @@ import torch
 
 from . import _lib
 from . import bigfft as _big
+from . import fused as _fused      # (the fused host path; it reads this module back at call time)
+from .fused import rows_of as _rows
 
 _DT = {torch.bfloat16: 0, torch.float16: 1}
 FUSED_SEQLENS = (256, 512, 1024, 4096, 8192, 16384, 32768)
@@ -142,11 +144,10 @@ def reload_env():
 _REF_BUFFER = re.compile(r"^(f_(\d+|sqrt_N)_i?fft(_real|_imag)?|twiddle_factors_i?fft(_\w+)?|twid)$")
 
 
-def _conv(plan, u, kf, pregate, postgate, conj):
+def _conv(plan, u, kf, pregate, postgate, conj, rows=0):
     B, H, L = u.shape
     y = torch.empty_like(u)
-    _lib.check(_lib.lib().ffc_conv_fwd(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
-                                       _lib.ptr(y), B, H, L, int(conj), _lib.stream_ptr()), "ffc_conv_fwd")
+    _fused.forward(plan, B, H, L, _rows(u), kf, _rows(pregate), _rows(postgate), _rows(y), rows=rows, conj=conj)
     return y
 
 
@@ -167,11 +168,7 @@ class _SeqlenOnly:
 
 
 def _conv_sparse(plan, u, kf, pregate, postgate, conj, rows):
-    B, H, L = u.shape
-    y = torch.empty_like(u)
-    _lib.check(_lib.lib().ffc_conv_fwd_sparse(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
-                                              _lib.ptr(y), B, H, L, int(conj), rows, _lib.stream_ptr()), "ffc_conv_fwd_sparse")
-    return y
+    return _conv(plan, u, kf, pregate, postgate, conj, rows)
 
 
 # FFC_SPARSE_BWD=0 (read by reload_env): the dense recomputing backward + torch mask on the frequency-sparse route, for A/B runs
@@ -181,9 +178,7 @@ _SPARSE_BWD = _os.environ.get("FFC_SPARSE_BWD", "1") != "0"
 def _bwd_sparse(plan, dout, u, kf, pregate, postgate, rows, ws, du, dpre, dpost):
     """fused backward of the compute-skipping route (ffc_conv_bwd_sparse): du / dpre / dpost and the LIVE rows of the dk_f slabs in ws"""
     B, H, L = u.shape
-    _lib.check(_lib.lib().ffc_conv_bwd_sparse(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
-                                              _lib.ptr(du), _lib.ptr(dpre), _lib.ptr(dpost), _lib.ptr(ws), None, B, H, L, rows,
-                                              _lib.stream_ptr()), "ffc_conv_bwd_sparse")
+    _fused.backward(plan, B, H, L, _rows(dout), _rows(u), kf, _rows(pregate), _rows(postgate), _rows(du), _rows(dpre), _rows(dpost), ws, rows=rows)
 
 
 def _ifft_grad_sparse(plan, ws, mask, rows, B, H, k_len, device):
@@ -248,7 +243,7 @@ SPECTRUM_FALLBACKS = {"budget": 0, "oom": 0}
 
 
 def _spectrum_buffer(plan, B, H, device, gated=True, mode=True):
-    """Buffer for the spectra FFT(u * pregate) that the forward pass keeps for the backward pass (ffc_conv_fwd_z / ffc_conv_bwd_z),
+    """Buffer for the spectra FFT(u * pregate) that the forward pass keeps for the backward pass (fused.forward / fused.backward),
     or None: no memory for it (the caller then takes the recomputing path, like the reference).  Every fused plan has the path:
     [H][pair][fft size] complex values, for the single-tile sizes (fft <= 2048) one 4 KB slot per tile and pass."""
     # single-tile sizes without gates: not worth it (measured at B64 H768, fwd + bwd: fft 256 +5 %, 1024 +-0; gated -9 % / -17 %
@@ -266,25 +261,6 @@ def _spectrum_buffer(plan, B, H, device, gated=True, mode=True):
     except torch.cuda.OutOfMemoryError:
         SPECTRUM_FALLBACKS["oom"] += 1
         return None
-
-
-def _conv_save(plan, u, kf, pregate, postgate, z, yraw=None):
-    B, H, L = u.shape
-    y = torch.empty_like(u)
-    _lib.check(_lib.lib().ffc_conv_fwd_z(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(y),
-                                         _lib.ptr(z), _lib.ptr(yraw), B, H, L, 0, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_z")
-    return y
-
-
-def _conv_res(plan, u, kf, pregate, postgate, residual, z=None, yraw=None):
-    """y = postgate * conv(u * pregate, k) + residual, the residual added in the kernel's output epilogue (ffc_conv_fwd_res);
-    z / yraw as _conv_save (yraw: the output before gate and residual)"""
-    B, H, L = u.shape
-    y = torch.empty_like(u)
-    _lib.check(_lib.lib().ffc_conv_fwd_res(plan.handle, _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(residual),
-                                           _lib.ptr(y), _lib.ptr(z), _lib.ptr(yraw), B, H, L, 0, 0, 0, 0, 0, 0, _lib.stream_ptr()),
-               "ffc_conv_fwd_res")
-    return y
 
 
 def _kernel_fft(plan, k):
@@ -505,7 +481,9 @@ class _TorchOps:
         """inner forward that also keeps the inner spectra (None when the inner plan has no such path)"""
         plan = self._plan(M)
         z = _spectrum_buffer(plan, x.shape[0], x.shape[1], self.device, True, "always")      # charged once, at module level
-        return (_conv(plan, x, kf, None, None, False), None) if z is None else (_conv_save(plan, x, kf, None, None, z), z)
+        y = torch.empty_like(x)
+        _fused.forward(plan, *x.shape, _rows(x), kf, _fused.NULL, _fused.NULL, _rows(y), z=z)      # (no buffer: the plain forward)
+        return y, z
 
     def bwd(self, dt, M, xd, xu, kf, z=None):
         """fused inner backward on pair-plane rows: (input gradient rows, fp32 dk_f slabs); z = spectra kept by conv_save"""
@@ -647,17 +625,10 @@ def _big_backward(mod, dout, u, kf, pregate, postgate, k_len, kept=None, want_dk
         xu = xd          # (shape only, below)
     if mod._kf_keep is not None:
         # d/dk of (mask * FFT(k)): mask the fp32 inner dk_f partial sums (same row / position order as k_f) before the inverse
-        plan_m = ops._plan(M)
-        hp_m = xu.shape[1]
-        nsl = _lib.lib().ffc_dkf_slab_count(plan_m.handle, xu.shape[0], hp_m)
         m32 = _big_kf_mask(mod, fac, u.device, torch.float32)
-        ws[: nsl * hp_m * plan_m.kf_elems * 8].view(torch.float32).view(nsl, H, m32.shape[0], m32.shape[1], 2).mul_(m32[None, None, :, :, None])
+        _fused.dkf_slabs(ops._plan(M), ws, xu.shape[0], xu.shape[1]).view(-1, H, m32.shape[0], m32.shape[1], 2).mul_(m32[None, None, :, :, None])
     if want_dkf:
-        plan = ops._plan(M)
-        hp, nfl = xu.shape[1], xu.shape[1] * plan.kf_elems * 2
-        nslab = _lib.lib().ffc_dkf_slab_count(plan.handle, xu.shape[0], hp)
-        slabs = ws[: nslab * nfl * 4].view(torch.float32).view(nslab, hp, plan.kf_elems, 2)
-        dk = slabs[0] if nslab == 1 else slabs.sum(0)
+        dk = _fused.dkf_sum(ops._plan(M), ws, xu.shape[0], xu.shape[1])
     else:
         dk = _big.dk_from_slabs(ops, N, ws, xu.shape[0], H, k_len, None, fac)
     return _big_backward_tail(mod, ops, dt, N, yd, dk, u, dout, xu, yu, kf, pregate, B, H, L, M, fac, outs)
@@ -764,162 +735,93 @@ class _FlashFFTConvFn(torch.autograd.Function):
         ctx.rev = None if k_rev is None else (k_rev.shape[-1], k_rev.dtype)
         if k_rev is not None and (ctx.big or mod._folded or mod._kf_keep is not None):
             raise RuntimeError("FlashFFTConv: internal: k_rev on a route without the two-tensor kernels")
-        kept = None
         if ctx.big:
             out, kf, kept, ctx.fac, ctx.half = _big_forward_routed(mod, u, k, pregate, postgate, any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4)))
         else:
             plan = mod._get_plan(u.device, mod._plan_seqlen)
-            cache = mod.cache_kf and not k.requires_grad and not (k_rev is not None and k_rev.requires_grad)
-            kf = mod._cached_kf(k, k_rev) if cache else None
-            if kf is None and k_rev is not None:      # k -> k_f as a launch of its own, then the convolution entry points
-                kf = _kernel_fft_bi(plan, k, k_rev)
-                if cache:
-                    mod._kf_cache = (_kf_key2(k, k_rev), kf)
-            # one C-ABI call for k -> k_f + the convolution (ffc_conv_fwd_k) unless something sits between the two
-            # (a residual takes k -> k_f + ffc_conv_fwd_res: the one-call entry point has no addend)
-            one_call = kf is None and not mod._folded and mod._kf_keep is None and residual is None
-            if kf is None and not one_call:
-                kf = _kernel_fft(plan, _periodise_k(k, mod.seqlen) if mod._folded else k)
-                if mod._kf_keep is not None:       # frequency-sparse k_f (flashfftconv/sparse_conv.py)
-                    kf.mul_(mod._kf_mask(plan, kf.dtype)[None, :, None])
-                if mod.cache_kf and not k.requires_grad:
-                    mod._kf_cache = (_kf_key(k), kf)
-            # MI355X design (memory laid out for 288 GB of HBM): a training forward keeps every pair's spectrum
-            # FFT(u * pregate) (2x the bytes of u at L = N/2) so that the backward pass does not transform u a second time: its
-            # kernel runs two transforms per pair instead of three (fused backward -30 % at B16 H768 fft 32768,
-            # profiles/r03_spectrum.txt).  The gated form also keeps the output before the postgate multiply (1x the bytes
-            # of u): dpostgate = dout * that, instead of one more inverse transform of the spectrum.
-            # module.save_spectrum = False (or FFC_SAVE_SPECTRUM=0) keeps the reference's recomputing backward.
-            z = yraw = None
+            B, H, L = u.shape
+            # one C-ABI call for k -> k_f + the convolution (fused.forward_k) unless something sits between the two: a cached k_f, a second
+            # filter tensor, the folded row, the bin mask (a residual takes k -> k_f + the entry point with an addend: the one-call one has none)
+            one_call = (k_rev is None and not mod._folded and mod._kf_keep is None and residual is None
+                        and not (mod.cache_kf and _fused.cached_kf(mod, k) is not None))
+            kf = None if one_call else _fused.kf_for(mod, plan, k, k_rev)      # k -> k_f as a launch of its own
             rows = 0 if one_call else _sparse_rows(mod, plan)      # low-pass k_f: the forward kernel that skips the all-zero spectrum rows
             ctx.sparse_rows = rows      # the backward takes the live-row kernels exactly where this call took _conv_sparse
-            if rows:
-                out = _conv_sparse(plan, u, kf, pregate, postgate, False, rows)
-            elif mod.training and mod.save_spectrum and _recording() and any(ctx.needs_input_grad[i] for i in (0, 1, 3, 4)):
-                # Gated single-tile sizes, opt-in (fft <= _Y_ONLY_MAX, round 6): keep ONLY the output before the postgate; the backward
-                # transforms u * pregate again (see _Y_ONLY_MAX: a third less kept memory at the same fwd + bwd time +- 3 %).
-                y_only = ctx.gated and plan.seqlen <= _Y_ONLY_MAX
-                if not y_only:
-                    z = _spectrum_buffer(plan, u.shape[0], u.shape[1], u.device, ctx.gated, mod.save_spectrum)
-                if (z is not None or y_only) and ctx.gated:
-                    try:
-                        yraw = torch.empty_like(u)
-                    except torch.cuda.OutOfMemoryError:
-                        z = None
+            # what a training forward keeps for the backward: fused.keep (nothing on the compute-skipping route).  Gated single-tile sizes,
+            # opt-in (fft <= _Y_ONLY_MAX, round 6): keep ONLY the output before the postgate; the backward transforms u * pregate again
+            # (see _Y_ONLY_MAX: a third less kept memory at the same fwd + bwd time +- 3 %).
+            g = ctx.needs_input_grad      # (u, k, -, pregate, postgate)
+            kept = z, yraw = _fused.keep(mod, plan, B, H, u, ctx.gated, not rows and mod.training and _recording() and (g[0] or g[1] or g[3] or g[4]),
+                                         ctx.gated and plan.seqlen <= _Y_ONLY_MAX)
             if one_call:
-                B, H, L = u.shape
-                k32 = k if (k.dtype == torch.float32 and k.is_contiguous()) else k.detach().to(torch.float32).contiguous()
-                kf = torch.empty(H, plan.kf_elems, 2, dtype=plan.dtype, device=u.device)
-                out = torch.empty_like(u)
-                _lib.check(_lib.lib().ffc_conv_fwd_k(plan.handle, _lib.ptr(k32), k32.shape[-1], _lib.ptr(kf), _lib.ptr(u), _lib.ptr(pregate),
-                                                     _lib.ptr(postgate), _lib.ptr(out), _lib.ptr(z), _lib.ptr(yraw), B, H, L,
-                                                     _lib.stream_ptr()), "ffc_conv_fwd_k")
-                if mod.cache_kf and not k.requires_grad:
-                    mod._kf_cache = (_kf_key(k), kf)
-            elif residual is not None:
-                if rows:
+                out, kf = _fused.forward_k(mod, plan, k, u, pregate, postgate, z, yraw)
+            elif rows:
+                if residual is not None:
                     raise RuntimeError("FlashFFTConv: internal: residual on the compute-skipping frequency-sparse kernel")
-                out = _conv_res(plan, u, kf, pregate, postgate, residual, z, yraw)
-            elif not rows:
-                out = (_conv(plan, u, kf, pregate, postgate, False) if z is None and yraw is None
-                       else _conv_save(plan, u, kf, pregate, postgate, z, yraw))
-        if mod.training:  # reference saves for backward only in training mode (conv.py:587-588)
-            # (z, yraw: saved tensors, released with the graph and kept by retain_graph like the others)
-            if ctx.big:
-                extra = () if kept is None else tuple(t for t in kept if t is not None)
-                ctx.kept_layout = None if kept is None else tuple(t is not None for t in kept)
+                out = _conv_sparse(plan, u, kf, pregate, postgate, False, rows)
             else:
-                extra = tuple(t for t in (z, yraw) if t is not None)      # (z, yraw) | (z,) | (yraw,): gated single-tile sizes keep y_raw alone
-                ctx.kept_z = z is not None
+                out = torch.empty_like(u)
+                _fused.forward(plan, B, H, L, _rows(u), kf, _rows(pregate), _rows(postgate), _rows(out), _rows(residual), z, yraw)
+        if mod.training:  # reference saves for backward only in training mode (conv.py:587-588)
+            # (z, yraw / what an HBM-level route kept: saved tensors, released with the graph and kept by retain_graph like the others;
+            # gated single-tile sizes may keep y_raw alone)
+            ctx.kept_layout, extra = _fused.pack_kept(kept)
             ctx.save_for_backward(*(((u, kf, pregate, postgate) if ctx.gated else (u, kf)) + extra))
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        if not ctx.saved_tensors:
+        saved = ctx.saved_tensors      # (read once: every access unpacks the saved tensors again)
+        if not saved:
             raise RuntimeError("FlashFFTConv: backward needs module.training=True at forward time")
         rev = []      # dk_rev, when the call had a k_rev
-        with _dev_ctx(ctx.saved_tensors[0].device):
-            grads = _FlashFFTConvFn._backward(ctx, dout, rev)
+        with _dev_ctx(saved[0].device):
+            grads = _FlashFFTConvFn._backward(ctx, dout, saved, rev)
         # y = (...) + residual: the residual's gradient is dout itself; the other gradients never see it
         # (every caller passes the residual and k_rev slots, None included)
         return grads + (dout if ctx.needs_input_grad[5] else None, rev[0] if rev else None)
 
     @staticmethod
-    def _backward(ctx, dout, rev_out=None):
+    def _backward(ctx, dout, saved, rev_out):
         dout = dout.contiguous()
-        z = yraw = None
         if ctx.gated:
-            u, kf, pregate, postgate = ctx.saved_tensors[:4]
-            if len(ctx.saved_tensors) > 4:
-                z, yraw = ctx.saved_tensors[4:6] if getattr(ctx, "kept_z", True) else (None, ctx.saved_tensors[4])
+            u, kf, pregate, postgate = saved[:4]
+            kept = _fused.unpack_kept(ctx.kept_layout, saved[4:])
         else:
-            (u, kf), pregate, postgate = ctx.saved_tensors[:2], None, None
-            z = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
+            (u, kf), pregate, postgate = saved[:2], None, None
+            kept = _fused.unpack_kept(ctx.kept_layout, saved[2:])
+        mod = ctx.mod
         if ctx.big:
-            kept = None
-            if getattr(ctx, "kept_layout", None) is not None:
-                it = iter(ctx.saved_tensors[4 if ctx.gated else 2:])
-                kept = tuple(next(it) if present else None for present in ctx.kept_layout)
-            du, dk, dpre, dpost = _big_backward(ctx.mod, dout, u, kf, pregate, postgate, ctx.k_len, kept, False, ctx.fac, ctx.half)
+            du, dk, dpre, dpost = _big_backward(mod, dout, u, kf, pregate, postgate, ctx.k_len, kept, False, ctx.fac, ctx.half)
             return du, dk.to(ctx.k_dtype), None, dpre, dpost
-        plan = ctx.mod._get_plan(u.device, ctx.mod._plan_seqlen)
+        z, yraw = kept
+        plan = mod._get_plan(u.device, mod._plan_seqlen)
         B, H, L = u.shape
-        lib = _lib.lib()
-        k_len = plan.seqlen if ctx.mod._folded else ctx.k_len
         # one fused launch: du (+ dpregate, dpostgate when gated) + fp32 dk_f partial sums; then dk_f -> dk
         ws = torch.empty(_ws_bytes(plan, B, H), dtype=torch.uint8, device=u.device)
         du = torch.empty_like(u)
         dpre = torch.empty_like(u) if ctx.gated else None
         dpost = torch.empty_like(u) if ctx.gated else None
-        if not ctx.mod._folded and ctx.mod._kf_keep is None and ctx.rev is None:
-            # one C-ABI call: fused backward (on the saved spectra when there are any) + dk_f -> dk (ffc_conv_bwd_k)
-            dk = torch.empty(H, k_len, dtype=torch.float32, device=u.device)
-            _lib.check(lib.ffc_conv_bwd_k(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate),
-                                          _lib.ptr(du), _lib.ptr(dpre), _lib.ptr(dpost), _lib.ptr(ws), _lib.ptr(z), _lib.ptr(yraw), _lib.ptr(dk),
-                                          k_len, B, H, L, _lib.stream_ptr()), "ffc_conv_bwd_k")
+        if not mod._folded and mod._kf_keep is None and ctx.rev is None:
+            # one C-ABI call: fused backward (on the saved spectra when there are any) + dk_f -> dk (fused.backward_k)
+            dk = _fused.backward_k(plan, dout, u, kf, pregate, postgate, du, dpre, dpost, ws, z, yraw, ctx.k_len)
             if dk.dtype != ctx.k_dtype:
                 dk = dk.to(ctx.k_dtype)
-            return (du, dk, None, dpre, dpost) if ctx.gated else (du, dk, None, None, None)
-        rows = getattr(ctx, "sparse_rows", 0) if _SPARSE_BWD else 0
+            return du, dk, None, dpre, dpost
+        rows = ctx.sparse_rows if _SPARSE_BWD else 0
         if rows:
             # frequency-sparse route: the recomputing kernel on the live spectrum rows, then dk_f -> dk on the live rows with the bin
             # mask applied by selection (no full slabs written, no torch pass over them)
             _bwd_sparse(plan, dout, u, kf, pregate, postgate, rows, ws, du, dpre, dpost)
-            dk = _ifft_grad_sparse(plan, ws, ctx.mod._kf_mask(plan, torch.float32), rows, B, H, k_len, u.device).to(ctx.k_dtype)
-            return (du, dk, None, dpre, dpost) if ctx.gated else (du, dk, None, None, None)
-        if (z is not None or yraw is not None) and ctx.gated:
-            # dpostgate = dout * y_raw out of the kernel's dout row load (round 3: a torch elementwise kernel, 3 x |u| bytes more)
-            _lib.check(lib.ffc_conv_bwd_zy(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate),
-                                           _lib.ptr(postgate), _lib.ptr(du), _lib.ptr(dpre), _lib.ptr(dpost), _lib.ptr(ws), _lib.ptr(z),
-                                           _lib.ptr(yraw), B, H, L, 0, 0, 0, 0, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_bwd_zy")
-        elif z is not None:
-            _lib.check(lib.ffc_conv_bwd_z(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate),
-                                          _lib.ptr(postgate), _lib.ptr(du), _lib.ptr(dpre), None, _lib.ptr(ws), _lib.ptr(z),
-                                          B, H, L, 0, 0, 0, 0, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_bwd_z")
-        else:
-            _lib.check(lib.ffc_conv_bwd_gated(plan.handle, _lib.ptr(dout), _lib.ptr(u), _lib.ptr(kf), _lib.ptr(pregate),
-                                              _lib.ptr(postgate), _lib.ptr(du), _lib.ptr(dpre), _lib.ptr(dpost), _lib.ptr(ws),
-                                              B, H, L, _lib.stream_ptr()), "ffc_conv_bwd_gated")
-        if ctx.mod._kf_keep is not None:
+            dk = _ifft_grad_sparse(plan, ws, mod._kf_mask(plan, torch.float32), rows, B, H, ctx.k_len, u.device).to(ctx.k_dtype)
+            return du, dk, None, dpre, dpost
+        _fused.backward(plan, B, H, L, _rows(dout), _rows(u), kf, _rows(pregate), _rows(postgate), _rows(du), _rows(dpre), _rows(dpost), ws, z, yraw)
+        if mod._kf_keep is not None:
             # d/dk of (mask * FFT(k)): mask the fp32 dk_f partial sums (same internal order as k_f) before the inverse
-            nfl = H * plan.kf_elems * 2
-            slabs = ws[: (ws.numel() // 4 // nfl) * nfl * 4].view(torch.float32).view(-1, H, plan.kf_elems, 2)
-            nslab = lib.ffc_dkf_slab_count(plan.handle, B, H)
-            slabs[:nslab].mul_(ctx.mod._kf_mask(plan, torch.float32)[None, None, :, None])
-        if ctx.rev is not None:      # both halves of a bidirectional filter's gradient from one inverse
-            dk, dkr = _ifft_grad_bi(plan, ws, B, H, k_len, ctx.rev[0], u.device)
-            rev_out.append(dkr.to(ctx.rev[1]))
-        else:
-            dk = torch.empty(H, k_len, dtype=torch.float32, device=u.device)
-            _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, H, k_len, _lib.ptr(dk), _lib.stream_ptr()),
-                       "ffc_kernel_ifft_grad")
-        if ctx.mod._folded:      # chain rule of _periodise_k
-            n = ctx.mod.seqlen
-            dk = (dk[:, :n] + dk[:, n:])[:, :ctx.k_len]
-        dk = dk.to(ctx.k_dtype)
-        if not ctx.gated:
-            return du, dk, None, None, None
+            _fused.dkf_slabs(plan, ws, B, H).mul_(mod._kf_mask(plan, torch.float32)[None, None, :, None])
+        dk, dk_rev = _fused.dk_from(mod, plan, ws, B, H, ctx.k_len, ctx.k_dtype, ctx.rev)
+        if dk_rev is not None:
+            rev_out.append(dk_rev)
         return du, dk, None, dpre, dpost
 
 
@@ -1018,10 +920,6 @@ class FlashFFTConv(torch.nn.Module):
         HBM level around the fused 4096 kernel wins for longer rows (L = 128K: 7.1 vs 12.6 -- every pass of the multi-pass form
         re-reads all four input blocks).  fft 65536 stays on its 2 passes at every length (L = 64K: 6.7 vs 7.2)."""
         return self.seqlen == 131072 and not self._big and Lmax > 65536 and 131072 in MULTIPASS_SEQLENS and _ROUTE_BY_LENGTH
-
-    def _cached_kf(self, k, k_rev=None):
-        c = self._kf_cache
-        return c[1] if c is not None and c[0] == _kf_key2(k, k_rev) else None
 
     def _kf_mask(self, plan, dtype):
         """0/1 mask over k_f's internal positions keeping the natural frequencies |f| < self._kf_keep."""

@@ -10,7 +10,7 @@ The reference's callers build the gated long convolution out of separate kernels
     y = y * x2                                     # elementwise kernel
     y = y + flashfftconv(v.contiguous(), k2)       # M2-BERT with residual_long_conv=True: copy, second convolution, add kernel
 
-Here the three slices are handed to the gated FFT-conv kernel IN PLACE (batch-strided rows, ffc_conv_fwd_strided): v is the
+Here the three slices are handed to the gated FFT-conv kernel IN PLACE (batch-strided rows, flashfftconv/fused.py rows_of): v is the
 input, x1 the pregate, x2 the postgate, so the multiply kernels, the copy and their HBM round trips disappear, in the forward
 and in the backward (du / dpregate / dpostgate are written straight into the slices of d(uc), one launch; then the short
 convolution's own backward).  y = x2 * conv(x1 * v, k): the same function as the reference composition.
@@ -21,19 +21,15 @@ backward, writes du, dpregate, dpostgate through the last inverse level) as slic
 
 With k_res (the M2 residual long convolution, monarch_mixer_sequence_mixer_flashfftconv.py:151-175) y = x2 * conv(x1 * v, k) +
 conv(v, k_res) in two launches: conv(v, k_res) reading the v slice in place, then the gated kernel with that result as the addend of its
-output epilogue (ffc_conv_fwd_res) -- no copy of v and no add kernel."""
+output epilogue (fused.forward's addend) -- no copy of v and no add kernel."""
 import torch
 
-from . import _lib
-from .conv import (FlashFFTConv, _check_inputs, _kernel_fft, _periodise_k, _spectrum_buffer, _kf_key, _apply_noting_grad_mode, _recording,
-                   _big_forward_routed, _big_backward, _dev_ctx, _TorchOps, _kernel_fft_bi, _ifft_grad_bi, _compose_k_full, _kf_key2,
-                   _check_k_rev)
+from . import fused as _fused
+from .fused import rows_of as _rows
+from .conv import (FlashFFTConv, _check_inputs, _apply_noting_grad_mode, _recording, _big_forward_routed, _big_backward, _dev_ctx,
+                   _ws_bytes, _TorchOps, _compose_k_full, _check_k_rev)
 from . import bigfft as _bigfft
 from .depthwise_1d import FlashDepthWiseConv1d
-
-
-def _slice_ptr(t, j, D, L):
-    return _lib.ctypes.c_void_p(t.data_ptr() + j * D * L * t.element_size())
 
 
 class _GatedSlicesFn(torch.autograd.Function):
@@ -48,130 +44,60 @@ class _GatedSlicesFn(torch.autograd.Function):
         plan = mod._get_plan(uc.device, mod._plan_seqlen)
         if (k_rev is not None or k_res_rev is not None) and mod._folded:
             raise RuntimeError("FlashHyenaOp: internal: a reversed filter on a folded plan")
-        with torch.cuda.device(uc.device):
-            cache = mod.cache_kf and not k.requires_grad and not (k_rev is not None and k_rev.requires_grad)
-            kf = mod._cached_kf(k, k_rev) if cache else None      # inference cache, as FlashFFTConv
-            if kf is None:
-                if k_rev is not None:
-                    kf = _kernel_fft_bi(plan, k, k_rev)
-                else:
-                    kf = _kernel_fft(plan, _periodise_k(k, mod.seqlen) if mod._folded else k)
-                if cache:
-                    mod._kf_cache = (_kf_key2(k, k_rev), kf)
+        with _dev_ctx(uc.device):
+            kf = _fused.kf_for(mod, plan, k, k_rev)      # (inference cache, as FlashFFTConv)
             y = torch.empty(B, D, L, dtype=uc.dtype, device=uc.device)
-            sb = D3 * L
+            # u = v (slice 2), pregate = x1 (slice 0), postgate = x2 (slice 1), read in place
+            x1, x2, v = (_rows(uc, j * D * L, D3 * L) for j in range(3))
             kf_res = yu = None
             if k_res is not None:
                 # launch 1: yu = conv(v, k_res), v read in place; its k_f has a cache slot of its own (k and k_res would evict each other)
-                cache_res = mod.cache_kf and not k_res.requires_grad and not (k_res_rev is not None and k_res_rev.requires_grad)
-                c = getattr(mod, "_kf_cache_res", None) if cache_res else None
-                kf_res = c[1] if c is not None and c[0] == _kf_key2(k_res, k_res_rev) else None
-                if kf_res is None:
-                    if k_res_rev is not None:
-                        kf_res = _kernel_fft_bi(plan, k_res, k_res_rev)
-                    else:
-                        kf_res = _kernel_fft(plan, _periodise_k(k_res, mod.seqlen) if mod._folded else k_res)
-                    if cache_res:
-                        mod._kf_cache_res = (_kf_key2(k_res, k_res_rev), kf_res)
+                kf_res = _fused.kf_for(mod, plan, k_res, k_res_rev, "_kf_cache_res")
                 yu = torch.empty_like(y)
-                _lib.check(_lib.lib().ffc_conv_fwd_strided(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf_res), None, None, _lib.ptr(yu),
-                                                           B, D, L, 0, sb, 0, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_strided")
+                _fused.forward(plan, B, D, L, v, kf_res, _fused.NULL, _fused.NULL, _rows(yu))
             # training: keep the spectra FFT(x1 * v) and the output before the x2 multiply (FlashFFTConv.save_spectrum)
-            z = yraw = None
-            if mod.training and mod.save_spectrum and _recording() and any(ctx.needs_input_grad[:2]):
-                z = _spectrum_buffer(plan, B, D, uc.device, True, mod.save_spectrum)
-                if z is not None:
-                    try:
-                        yraw = torch.empty_like(y)
-                    except torch.cuda.OutOfMemoryError:
-                        z = None
-            if yu is not None:
-                # launch 2: the gated kernel with yu as the addend of its output epilogue (z / yraw nullable: the output before x2 and yu)
-                _lib.check(_lib.lib().ffc_conv_fwd_res(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf), _slice_ptr(uc, 0, D, L),
-                                                       _slice_ptr(uc, 1, D, L), _lib.ptr(yu), _lib.ptr(y), _lib.ptr(z), _lib.ptr(yraw), B, D, L,
-                                                       0, sb, sb, sb, 0, 0, _lib.stream_ptr()), "ffc_conv_fwd_res")
-            elif z is None:
-                _lib.check(_lib.lib().ffc_conv_fwd_strided(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf), _slice_ptr(uc, 0, D, L),
-                                                           _slice_ptr(uc, 1, D, L), _lib.ptr(y), B, D, L, 0, sb, sb, sb, 0,
-                                                           _lib.stream_ptr()), "ffc_conv_fwd_strided")
-            else:
-                _lib.check(_lib.lib().ffc_conv_fwd_z(plan.handle, _slice_ptr(uc, 2, D, L), _lib.ptr(kf), _slice_ptr(uc, 0, D, L),
-                                                     _slice_ptr(uc, 1, D, L), _lib.ptr(y), _lib.ptr(z), _lib.ptr(yraw), B, D, L,
-                                                     sb, sb, sb, 0, _lib.stream_ptr()), "ffc_conv_fwd_z")
+            z, yraw = _fused.keep(mod, plan, B, D, y, True, mod.training and _recording() and any(ctx.needs_input_grad[:2]))
+            # launch 2 with k_res: the gated kernel with yu as the addend of its output epilogue (z / yraw: the output before x2 and yu)
+            _fused.forward(plan, B, D, L, v, kf, x1, x2, _rows(y), _rows(yu), z, yraw)
         ctx.mod, ctx.k_len, ctx.k_dtype = mod, k.shape[-1], k.dtype
         ctx.res = None if k_res is None else (k_res.shape[-1], k_res.dtype)
         ctx.rev = None if k_rev is None else (k_rev.shape[-1], k_rev.dtype)
         ctx.res_rev = None if k_res_rev is None else (k_res_rev.shape[-1], k_res_rev.dtype)
         if mod.training:
-            ctx.save_for_backward(*((uc, kf) + (() if z is None else (z, yraw)) + (() if kf_res is None else (kf_res,))))
+            ctx.kept_layout, extra = _fused.pack_kept((z, yraw, kf_res))
+            ctx.save_for_backward(uc, kf, *extra)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        if not ctx.saved_tensors:
+        saved = ctx.saved_tensors
+        if not saved:
             raise RuntimeError("FlashHyenaOp: backward needs module.training=True at forward time")
-        uc, kf = ctx.saved_tensors[:2]
-        rest = ctx.saved_tensors[2:]
-        kf_res = None
-        if ctx.res is not None:
-            rest, kf_res = rest[:-1], rest[-1]
-        z, yraw = rest[:2] if len(rest) >= 2 else (None, None)
+        uc, kf = saved[:2]
+        z, yraw, kf_res = _fused.unpack_kept(ctx.kept_layout, saved[2:])
         mod = ctx.mod
         B, D3, L = uc.shape
         D = D3 // 3
         plan = mod._get_plan(uc.device, mod._plan_seqlen)
-        lib = _lib.lib()
-        with torch.cuda.device(uc.device):
+        with _dev_ctx(uc.device):
             dy = dy.contiguous()
             duc = torch.empty_like(uc)
-            ws = torch.empty(lib.ffc_dkf_workspace_bytes(plan.handle, B, D), dtype=torch.uint8, device=uc.device)
-            sb = D3 * L
+            ws = torch.empty(_ws_bytes(plan, B, D), dtype=torch.uint8, device=uc.device)
             # u = v (slice 2), pregate = x1 (slice 0), postgate = x2 (slice 1); gradients land in the same slices of duc
-            if z is not None:
-                # d x2 = dy * (output before the x2 multiply): written into its slice of duc by the kernel's dy row load
-                _lib.check(lib.ffc_conv_bwd_zy(plan.handle, _lib.ptr(dy), _slice_ptr(uc, 2, D, L), _lib.ptr(kf),
-                                               _slice_ptr(uc, 0, D, L), _slice_ptr(uc, 1, D, L), _slice_ptr(duc, 2, D, L),
-                                               _slice_ptr(duc, 0, D, L), _slice_ptr(duc, 1, D, L), _lib.ptr(ws), _lib.ptr(z), _lib.ptr(yraw),
-                                               B, D, L, 0, sb, sb, sb, sb, sb, sb, _lib.stream_ptr()), "ffc_conv_bwd_zy")
-            else:
-              _lib.check(lib.ffc_conv_bwd_gated_strided(plan.handle, _lib.ptr(dy), _slice_ptr(uc, 2, D, L), _lib.ptr(kf),
-                                                      _slice_ptr(uc, 0, D, L), _slice_ptr(uc, 1, D, L), _slice_ptr(duc, 2, D, L),
-                                                      _slice_ptr(duc, 0, D, L), _slice_ptr(duc, 1, D, L), _lib.ptr(ws), B, D, L,
-                                                      0, sb, sb, sb, sb, sb, sb, _lib.stream_ptr()), "ffc_conv_bwd_gated_strided")
-            k_len = plan.seqlen if mod._folded else ctx.k_len
-            dk_rev = dk_res_rev = None
-            if ctx.rev is not None:
-                dk, dk_rev = _ifft_grad_bi(plan, ws, B, D, k_len, ctx.rev[0], uc.device)
-                dk_rev = dk_rev.to(ctx.rev[1])
-            else:
-                dk = torch.empty(D, k_len, dtype=torch.float32, device=uc.device)
-                _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, k_len, _lib.ptr(dk), _lib.stream_ptr()),
-                           "ffc_kernel_ifft_grad")
-            if mod._folded:
-                n = mod.seqlen
-                dk = (dk[:, :n] + dk[:, n:])[:, :ctx.k_len]
-            dk_res = None
+            # (with z: d x2 = dy * (output before the x2 multiply), written into its slice of duc by the kernel's dy row load)
+            x1, x2, v = (_rows(uc, j * D * L, D3 * L) for j in range(3))
+            dx1, dx2, dv = (_rows(duc, j * D * L, D3 * L) for j in range(3))
+            _fused.backward(plan, B, D, L, _rows(dy), v, kf, x1, x2, dv, dx1, dx2, ws, z, yraw)
+            dk, dk_rev = _fused.dk_from(mod, plan, ws, B, D, ctx.k_len, ctx.k_dtype, ctx.rev)
+            dk_res = dk_res_rev = None
             if kf_res is not None:
                 # the residual branch yu = conv(v, k_res): the ungated fused backward on (dy, v in place, kf_res) -> dk_res and a (B, D, L)
                 # input gradient, added into v's slice of duc (the workspace is free again: stream order)
-                dv = torch.empty_like(dy)
-                _lib.check(lib.ffc_conv_bwd_gated_strided(plan.handle, _lib.ptr(dy), _slice_ptr(uc, 2, D, L), _lib.ptr(kf_res), None, None,
-                                                          _lib.ptr(dv), None, None, _lib.ptr(ws), B, D, L, 0, sb, 0, 0, 0, 0, 0,
-                                                          _lib.stream_ptr()), "ffc_conv_bwd_gated_strided")
-                kr_len = plan.seqlen if mod._folded else ctx.res[0]
-                if ctx.res_rev is not None:
-                    dk_res, dk_res_rev = _ifft_grad_bi(plan, ws, B, D, kr_len, ctx.res_rev[0], uc.device)
-                    dk_res_rev = dk_res_rev.to(ctx.res_rev[1])
-                else:
-                    dk_res = torch.empty(D, kr_len, dtype=torch.float32, device=uc.device)
-                    _lib.check(lib.ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), B, D, kr_len, _lib.ptr(dk_res), _lib.stream_ptr()),
-                               "ffc_kernel_ifft_grad")
-                if mod._folded:
-                    n = mod.seqlen
-                    dk_res = (dk_res[:, :n] + dk_res[:, n:])[:, :ctx.res[0]]
-                dk_res = dk_res.to(ctx.res[1])
-                duc[:, 2 * D:].add_(dv)
-        return duc, dk.to(ctx.k_dtype), None, dk_res, dk_rev, dk_res_rev      # (the caller passes every filter slot, None included)
+                dvr = torch.empty_like(dy)
+                _fused.backward(plan, B, D, L, _rows(dy), v, kf_res, _fused.NULL, _fused.NULL, _rows(dvr), _fused.NULL, _fused.NULL, ws)
+                dk_res, dk_res_rev = _fused.dk_from(mod, plan, ws, B, D, ctx.res[0], ctx.res[1], ctx.res_rev)
+                duc[:, 2 * D:].add_(dvr)
+        return duc, dk, None, dk_res, dk_rev, dk_res_rev      # (the caller passes every filter slot, None included)
 
 
 class _GatedSlicesBigFn(torch.autograd.Function):
@@ -198,11 +124,11 @@ class _GatedSlicesBigFn(torch.autograd.Function):
         ctx.mod, ctx.k_len, ctx.k_dtype, ctx.fac, ctx.half = mod, k.shape[-1], k.dtype, fac, half
         ctx.layouts = ctx.res = None
         if mod.training:
-            saved, layouts = [uc], []
+            saved, ctx.layouts = [uc], []
             for kf_, kept_ in ((kf, kept),) + (() if res is None else (res[:2],)):
-                layouts.append(None if kept_ is None else tuple(t is not None for t in kept_))
-                saved += [kf_] + ([] if kept_ is None else [t for t in kept_ if t is not None])
-            ctx.layouts = layouts
+                layout, there = _fused.pack_kept(kept_)
+                ctx.layouts.append(layout)
+                saved += (kf_,) + there
             ctx.res = None if res is None else res[2:]
             ctx.save_for_backward(*saved)
         return y
@@ -213,10 +139,7 @@ class _GatedSlicesBigFn(torch.autograd.Function):
             raise RuntimeError("FlashHyenaOp: backward needs module.training=True at forward time")
         it = iter(ctx.saved_tensors)
         uc = next(it)
-        calls = []
-        for layout in ctx.layouts:
-            kf = next(it)
-            calls.append((kf, None if layout is None else tuple(next(it) if present else None for present in layout)))
+        calls = [(next(it), _fused.unpack_kept(layout, it)) for layout in ctx.layouts]
         mod = ctx.mod
         B, D3, L = uc.shape
         D = D3 // 3

@@ -25,6 +25,9 @@ logic is exercised by world_size-2 gloo tests without a GPU.  The reference has 
 import torch
 import torch.distributed as dist
 
+from .conv import _check_inputs, _dev_ctx, _NOOP_CTX
+from .fused import pack_kept, unpack_kept
+
 
 def head_range(H, rank, world):
     """Contiguous, balanced head partition (first H % world ranks get one extra head)."""
@@ -229,8 +232,8 @@ class _HipOps:
     SLICES = True
 
     def __init__(self, mod, device):
-        from . import conv as C, _lib
-        self.C, self.L, self.mod = C, _lib, mod
+        from . import conv as C, fused
+        self.C, self.F, self.mod = C, fused, mod
         self.plan = mod._get_plan(device, mod._plan_seqlen)
 
     def kernel_fft(self, k):                       # (h, Lk) fp32 -> (h, kf_elems, 2) dtype, internal order
@@ -238,60 +241,31 @@ class _HipOps:
             return torch.empty(0, self.plan.kf_elems, 2, dtype=self.plan.dtype, device=k.device)
         return self.C._kernel_fft(self.plan, k)
 
-    def _sp(self, t, g0):
-        """pointer to head g0 of a contiguous (B, H, L) tensor (None stays None)"""
-        import ctypes
-        return None if t is None else ctypes.c_void_p(t.data_ptr() + g0 * t.shape[-1] * t.element_size())
-
     def conv_slice(self, u, kf, pre, post, out, g0, g1, keep):
         """out[:, g0:g1] = conv of heads [g0, g1) with their k_f rows `kf`; keep: also store the spectra (+ the output before the
         postgate) for backward_slice -> (z, yraw) or None"""
-        L, lib = self.L, self.L.lib()
         B, H, Lu = u.shape
-        hg, sb = g1 - g0, H * Lu
-        if hg == 0:
+        if g1 == g0:
             return None
-        z = yraw = None
-        if keep and self.mod.save_spectrum:
-            z = self.C._spectrum_buffer(self.plan, B, hg, u.device, pre is not None, self.mod.save_spectrum)
-            if z is not None and pre is not None:
-                try:
-                    yraw = torch.empty(B, hg, Lu, dtype=u.dtype, device=u.device)
-                except torch.cuda.OutOfMemoryError:      # same fallback as the single-rank module (ADVICE r03)
-                    z = None
-        if z is None:
-            L.check(lib.ffc_conv_fwd_strided(self.plan.handle, self._sp(u, g0), L.ptr(kf), self._sp(pre, g0), self._sp(post, g0),
-                                             self._sp(out, g0), B, hg, Lu, 0, sb, sb, sb, sb, L.stream_ptr()), "ffc_conv_fwd_strided")
-            return None
-        L.check(lib.ffc_conv_fwd_z(self.plan.handle, self._sp(u, g0), L.ptr(kf), self._sp(pre, g0), self._sp(post, g0), self._sp(out, g0),
-                                   L.ptr(z), L.ptr(yraw), B, hg, Lu, sb, sb, sb, sb, L.stream_ptr()), "ffc_conv_fwd_z")
-        return (z, yraw)
+        # (the OutOfMemoryError fallback of the single-rank module, ADVICE r03: fused.keep)
+        z, yraw = self.F.keep(self.mod, self.plan, B, g1 - g0, u, pre is not None, keep)
+        u, pre, post, out = (self.F.rows_of(t, g0 * Lu, H * Lu) for t in (u, pre, post, out))      # head g0 of contiguous (B, H, L) tensors
+        self.F.forward(self.plan, B, g1 - g0, Lu, u, kf, pre, post, out, z=z, yraw=yraw)
+        return None if z is None else (z, yraw)
 
     def backward_slice(self, dout, u, kf, pre, post, du, dpre, dpost, g0, g1, kept=None):
         """gradients of heads [g0, g1) written into their slices of du / dpre / dpost -> dk_f (hg, kf_elems, 2) fp32, summed over
         the local batch"""
-        lib, L = self.L.lib(), self.L
         B, H, Lu = u.shape
-        hg, sb = g1 - g0, H * Lu
+        hg = g1 - g0
         if hg == 0:
             return torch.empty(0, self.plan.kf_elems, 2, dtype=torch.float32, device=u.device)
-        ws = torch.empty(lib.ffc_dkf_workspace_bytes(self.plan.handle, B, hg), dtype=torch.uint8, device=u.device)
-        if kept is not None and pre is not None:
-            z, yraw = kept
-            L.check(lib.ffc_conv_bwd_zy(self.plan.handle, self._sp(dout, g0), self._sp(u, g0), L.ptr(kf), self._sp(pre, g0), self._sp(post, g0),
-                                        self._sp(du, g0), self._sp(dpre, g0), self._sp(dpost, g0), L.ptr(ws), L.ptr(z), L.ptr(yraw),
-                                        B, hg, Lu, sb, sb, sb, sb, sb, sb, sb, L.stream_ptr()), "ffc_conv_bwd_zy")
-        elif kept is not None:
-            L.check(lib.ffc_conv_bwd_z(self.plan.handle, self._sp(dout, g0), self._sp(u, g0), L.ptr(kf), None, None, self._sp(du, g0), None,
-                                       None, L.ptr(ws), L.ptr(kept[0]), B, hg, Lu, sb, sb, sb, sb, sb, sb, sb, L.stream_ptr()), "ffc_conv_bwd_z")
-        else:
-            L.check(lib.ffc_conv_bwd_gated_strided(self.plan.handle, self._sp(dout, g0), self._sp(u, g0), L.ptr(kf), self._sp(pre, g0),
-                                                   self._sp(post, g0), self._sp(du, g0), self._sp(dpre, g0), self._sp(dpost, g0), L.ptr(ws),
-                                                   B, hg, Lu, sb, sb, sb, sb, sb, sb, sb, L.stream_ptr()), "ffc_conv_bwd_gated_strided")
-        nslab = lib.ffc_dkf_slab_count(self.plan.handle, B, hg)
-        nfl = hg * self.plan.kf_elems * 2
-        slabs = ws[: nslab * nfl * 4].view(torch.float32).view(nslab, hg, self.plan.kf_elems, 2)
-        return slabs[0] if nslab == 1 else slabs.sum(0)
+        ws = torch.empty(self.C._ws_bytes(self.plan, B, hg), dtype=torch.uint8, device=u.device)
+        z, yraw = kept if kept is not None else (None, None)
+        rows = (self.F.rows_of(t, g0 * Lu, H * Lu) for t in (dout, u, pre, post, du, dpre, dpost))
+        dout, u, pre, post, du, dpre, dpost = rows
+        self.F.backward(self.plan, B, hg, Lu, dout, u, kf, pre, post, du, dpre, dpost, ws, z, yraw)
+        return self.F.dkf_sum(self.plan, ws, B, hg)
 
     # whole-tensor forms (one head group)
     def conv(self, u, kf, pre, post):
@@ -312,7 +286,7 @@ class _HipOps:
         return du, dpre, dpost, dkf
 
     def dk_from_dkf(self, dkf, Lk):                # (h, kf_elems, 2) fp32 -> (h, Lk) fp32
-        L = self.L
+        from . import _lib as L
         h = dkf.shape[0]
         dk = torch.empty(h, Lk, dtype=torch.float32, device=dkf.device)
         if h == 0:
@@ -427,13 +401,9 @@ class _BShardFn(torch.autograd.Function):
                 kepts.append(_conv_group(ops, u, kf, pre, post, out, g0, g1, do_keep))
         ctx.ops, ctx.group, ctx.Lk, ctx.k_dtype, ctx.gated, ctx.H, ctx.rows, ctx.groups = ops, group, Lk, k.dtype, pre is not None, H, rows, groups
         if training:
-            flat, layout = [], []
-            for kept in kepts:
-                layout.append(None if kept is None else tuple(t is not None for t in kept))
-                if kept is not None:
-                    flat += [t for t in kept if t is not None]
-            ctx.kept_layout = layout
-            ctx.save_for_backward(*(((u, pre, post) if pre is not None else (u,)) + tuple(kfs) + tuple(flat)))
+            packs = [pack_kept(kept) for kept in kepts]
+            ctx.kept_layout = [layout for layout, _ in packs]
+            ctx.save_for_backward(*(((u, pre, post) if pre is not None else (u,)) + tuple(kfs) + tuple(t for _, there in packs for t in there)))
         return out
 
     @staticmethod
@@ -448,9 +418,8 @@ class _BShardFn(torch.autograd.Function):
         groups, ops, rows = ctx.groups, ctx.ops, ctx.rows
         kfs, sv = sv[:len(groups)], sv[len(groups):]
         it = iter(sv)
-        kepts = [None if lay is None else tuple(next(it) if present else None for present in lay) for lay in ctx.kept_layout]
-        import contextlib
-        with (torch.cuda.device(u.device) if u.is_cuda else contextlib.nullcontext()):
+        kepts = [unpack_kept(lay, it) for lay in ctx.kept_layout]
+        with (_dev_ctx(u.device) if u.is_cuda else _NOOP_CTX):
             dout = dout.contiguous()
             rs = []
             if len(groups) == 1:
@@ -556,8 +525,7 @@ class BatchShardedFFTConv(torch.nn.Module):
         if not (getattr(ops, "SLICES", False) or getattr(ops, "GENERIC_SLICES", False)):
             ng = 1
         if self._ops is None:
-            from .conv import _check_inputs
             _check_inputs(conv, u, k, (pregate, postgate))
-            with torch.cuda.device(u.device):
+            with _dev_ctx(u.device):
                 return _BShardFn.apply(u, k, pregate, postgate, ops, self.group, training, keep, ng)
         return _BShardFn.apply(u, k, pregate, postgate, ops, self.group, training, keep, ng)
