@@ -80,6 +80,18 @@ struct ConvArgs {
   int64_t sba;
 };
 
+// Blocked rows (overlap-save form, ffc_conv_fwd_os / ffc_conv_bwd_dkf_os; single-pass sizes with an outer digit).  A tensor row of L
+// samples is cut into nblk blocks of S = N / 2 samples and every block is one plane of the N-point kernel: the kernel's batch is
+// ConvArgs::B = (tensor batch) * nblk, batch index i <-> tensor row b = i / nblk, block j = i % nblk, and ConvArgs::sbu / sby stay the
+// TENSOR's batch strides.  The window that comes in and the samples that go out have lengths of their own, so ConvArgs::L is not read
+// by the row copies of this form (the launcher sets it to N):
+//   in   window position n < N holds source sample j S + n, with `wrap` j S + n - N for n >= S (the previous block, at the circular
+//        negative lags); zero where that index is outside [0, L).  rows_load_os / rows_store_os; NC = NCH / 2 brings in n < S only.
+//   out  window positions n < S go to sample j S + n where it is < L (rows_out_os: half of the window's rows).
+struct OsRows {
+  int nblk, S, L, wrap;
+};
+
 // One pass of a multi-pass size (fft size N = R * M, M = GEO::N = N1 * Mi; HostPlan::R).  With n = n0 M + n1 Mi + mi and
 // f = k0 + R f', pass k0 computes the M-point circular convolution of
 //   x_k0[n1 Mi + mi] = W_N^{(n1 Mi + mi) k0} * sum_n0 W_R^{n0 k0} z[n0 M + n1 Mi + mi]
@@ -934,6 +946,116 @@ struct Body {
           }
           gstore8_rows((uint16_t*)a.y, b, h, a, a.sby, m, fast, ok, v);
         }
+      }
+    }
+  }
+
+  // ------------------------------------------------------------------ blocked rows (struct OsRows): the row copies of the overlap-save form
+  // Chunk i of a wave's slice starts at E row (i * 64) / CPR, a compile-time constant, and the chunks i >= NCH / 2 are the window
+  // positions n >= S -- the history half of a wrapped window.  So per chunk and plane the source index of window position 0 (the block's
+  // start, minus N for a history chunk) is a wave-uniform scalar, and so is whether the whole chunk lies outside [0, L): block 0 has no
+  // history, the ragged last block ends early, an odd batch has no second plane.  Inside a live chunk every index is >= 0; only `< L`
+  // is left per lane.  The integer division of the batch index runs once per plane and copy.
+  struct OsPlane { int64_t ro; int s0; bool ok; };      // tensor row (elements), first sample of the block, plane exists
+  static FFC_FN OsPlane os_plane(const ConvArgs& a, const OsRows& o, int64_t sb, int h, int pq, int pl) {
+    const int bi = 2 * pq + pl;
+    OsPlane P;
+    P.ok = bi < a.B;
+    const int b = P.ok ? bi / o.nblk : 0, j = P.ok ? bi - b * o.nblk : 0;
+    P.ro = (int64_t)b * sb + (int64_t)h * o.L;
+    P.s0 = j * o.S;
+    return P;
+  }
+  static FFC_FN int os_s0(const OsRows& o, const OsPlane& P, int i, bool in) { return P.s0 - ((in && o.wrap && i >= NCH / 2) ? GEO::N : 0); }
+  static FFC_FN bool os_dead(const OsRows& o, const OsPlane& P, int i, int s0) {
+    const int r0 = ((i * 64) / CPR) * GEO::Mi;      // first window position of the chunk's rows
+    return !P.ok || s0 + r0 < 0 || s0 + r0 >= o.L;
+  }
+  // 16-byte path (a.fast: L % 8 == 0, and S % 8 == 0 always): unconditional loads from a clamped position that is always inside the
+  // row -- a dead chunk re-reads the start of its tensor row -- zeroed at the LDS write, as the plain-row kernels do; else element-wise.
+  template <int NC>
+  static FFC_FN void rows_load_os(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un, RowRegsT<NC>& X) {
+    static_assert(GEO::OUTER, "blocked rows: sizes with an outer digit");
+    const i32 lane = B::opaque(B::lane());
+    const int fast = a.fast ? (a.stream ? 2 : 1) : 0;
+    const OsPlane P[2] = {os_plane(a, o, a.sbu, h, pq, 0), os_plane(a, o, a.sbu, h, pq, 1)};
+#pragma unroll
+    for (int i = 0; i < NC; i++) {
+      i32 idx = lane + i * 64;
+      i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+      const i32 n = row * GEO::Mi + m;
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        const int s0 = os_s0(o, P[pl], i, true);
+        const bool dead = os_dead(o, P[pl], i, s0);
+        const uint16_t* base = (const uint16_t*)a.u + P[pl].ro;
+        if (fast) {
+          const i32 n16 = B::imin(n + (dead ? -((i * 64) / CPR) * GEO::Mi : s0), o.L - 8) >> 3;
+          X.v[i][pl] = fast == 2 ? B::g_r128_nt(base, n16) : B::g_r128(base, n16);
+        } else {
+          u32 w[4];
+#pragma unroll
+          for (int q = 0; q < 4; q++) {
+            const i32 e0 = n + (s0 + 2 * q), e1 = n + (s0 + 2 * q + 1);
+            u32 lo = B::g_r16(base, e0, (e0 < o.L) && !dead);
+            u32 hi = B::g_r16(base, e1, (e1 < o.L) && !dead);
+            w[q] = lo | (hi << 16);
+          }
+          X.v[i][pl].x = w[0]; X.v[i][pl].y = w[1]; X.v[i][pl].z = w[2]; X.v[i][pl].w = w[3];
+        }
+      }
+    }
+  }
+  // zero what lies outside [0, L) / the batch, swizzle, write to E
+  template <int NC>
+  static FFC_FN void rows_store_os(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un, const RowRegsT<NC>& X) {
+    const i32 lane = B::opaque(B::lane());
+    const OsPlane P[2] = {os_plane(a, o, a.sbu, h, pq, 0), os_plane(a, o, a.sbu, h, pq, 1)};
+#pragma unroll
+    for (int i = 0; i < NC; i++) {
+      i32 idx = lane + i * 64;
+      i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+      pred sw;
+      i32 off = pair_off(row, m, &sw) + un.eb;
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        const int s0 = os_s0(o, P[pl], i, true);
+        U4 v = X.v[i][pl];
+        pred ok = ((row * GEO::Mi + m + s0) < o.L) && !os_dead(o, P[pl], i, s0);
+        v.x = B::sel(ok, v.x, B::uconst(0)); v.y = B::sel(ok, v.y, B::uconst(0));
+        v.z = B::sel(ok, v.z, B::uconst(0)); v.w = B::sel(ok, v.w, B::uconst(0));
+        U4 w;
+        w.x = B::sel(sw, v.z, v.x); w.y = B::sel(sw, v.w, v.y);
+        w.z = B::sel(sw, v.x, v.z); w.w = B::sel(sw, v.y, v.w);
+        B::lds_w128(off + pl * GEO::PLANE, w, B::ptrue());
+      }
+    }
+  }
+  template <int NC>
+  static FFC_FN void rows_in_os(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un) {
+    RowRegsT<NC> X;
+    rows_load_os<NC>(a, o, h, pq, un, X);
+    rows_store_os<NC>(a, o, h, pq, un, X);
+  }
+  // window positions n < S of E (the chunks i < NCH / 2) -> samples j S + n < L of a.y
+  static FFC_FN void rows_out_os(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un) {
+    const i32 lane = B::opaque(B::lane());
+    const int fast = a.fast ? (a.stream ? 2 : 1) : 0;
+    const OsPlane P[2] = {os_plane(a, o, a.sby, h, pq, 0), os_plane(a, o, a.sby, h, pq, 1)};
+#pragma unroll
+    for (int i = 0; i < NCH / 2; i++) {
+      i32 idx = lane + i * 64;
+      i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+      pred sw;
+      i32 off = pair_off(row, m, &sw) + un.eb;
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        U4 w = B::lds_r128(off + pl * GEO::PLANE);
+        U4 v;
+        v.x = B::sel(sw, w.z, w.x); v.y = B::sel(sw, w.w, w.y);
+        v.z = B::sel(sw, w.x, w.z); v.w = B::sel(sw, w.y, w.w);
+        // (gstore8's predicate is `position < L` of the tensor row: the ragged last block ends there)
+        gstore8((uint16_t*)a.y + P[pl].ro, row * GEO::Mi + m + P[pl].s0, o.L, fast, P[pl].ok, v);
       }
     }
   }
@@ -2444,10 +2566,13 @@ struct Body {
   }
   // GS: phase C stores the output rows itself (outer_inv_half<true>); instantiated for, and launched on, plain output rows only
   // PL: the input rows are plain too (ffc::plain_rows_ok): rows_load_pl / rows_store_pl, no gate, side-product or element-wise arm
-  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false>
-  static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0) {
+  // OS: blocked rows (struct OsRows `o`): the whole window comes in (rows_load_os / rows_store_os, full-height phase A) and only the
+  //     window positions n < S go out, so phase C runs its half-height form and rows_out_os moves half of the rows
+  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false>
+  static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0, OsRows o = OsRows()) {
     static_assert(!GS || (HALF && !RP && !SP && HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
     static_assert(!PL || GS, "plain input rows: a form of the direct-store kernels");
+    static_assert(!OS || !(HALF || PROF || RP || SZ || SP || GS || PL), "blocked rows: a form of the plain full-length kernel");
     constexpr int NC = HALF ? NCH / 2 : NCH;
     // HALF: the next pair's rows (32 VGPRs) are prefetched behind the last k_f load of phase B, so they
     // arrive during the last tile / phase C / the stores and no earlier in-order vmcnt wait is delayed.
@@ -2510,8 +2635,13 @@ struct Body {
         if constexpr (RP) {
           rows_in_rp<NC>(a, h, p, un, ps);
         } else if constexpr (!ROT) {
-          if constexpr (!PREFETCH) rows_load_sel<NC, PL>(a, h, p, un, X);
-          rows_store_sel<NC, PL>(a, h, p, un, X);
+          if constexpr (OS) {
+            rows_load_os<NC>(a, o, h, p, un, X);
+            rows_store_os<NC>(a, o, h, p, un, X);
+          } else {
+            if constexpr (!PREFETCH) rows_load_sel<NC, PL>(a, h, p, un, X);
+            rows_store_sel<NC, PL>(a, h, p, un, X);
+          }
         }
         B::lds_fence();      // (ROT: the pair's rows were written at the bottom of the previous iteration, or in the prologue)
         FFC_TICK(0)
@@ -2594,7 +2724,7 @@ struct Body {
           }
         }
       } else if (act) {
-        outer_stage<false, HALF, RP>(a.L, un, 1.0f, ps, a.flags);
+        outer_stage<false, HALF || OS, RP>(a.L, un, 1.0f, ps, a.flags);
         B::lds_fence();
         FFC_TICK(5)
         FFC_PRIO(2)
@@ -2606,7 +2736,8 @@ struct Body {
             else rows_out<NC, false>(ar, h, p, un);
           }
         }
-        if constexpr (RP) rows_out_rp<NC>(a, h, p, un, ps);
+        if constexpr (OS) rows_out_os(a, o, h, p, un);
+        else if constexpr (RP) rows_out_rp<NC>(a, h, p, un, ps);
         else rows_out<NC>(a, h, p, un);
         FFC_TICK(6)
       }
@@ -2630,8 +2761,8 @@ struct Body {
     conv_job<HALF, false, SZ, SP, GS, PL>(a, h, chunk);
   }
   // one (head, chunk) job; the tables are already in LDS.  RP: all passes of a multi-pass size
-  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false>
-  static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk) {
+  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false>
+  static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk, OsRows o = OsRows()) {
     const int wv = B::wave();
     Unit un;
     un.wq = wv % GEO::NW;
@@ -2641,7 +2772,7 @@ struct Body {
     int p1 = p0 + a.ppc;
     if (p1 > a.npair) p1 = a.npair;
     if constexpr (GEO::OUTER) {
-      outer_jobs<HALF, false, RP, SZ, SP, GS, PL>(a, h, p0, p1, u, un);
+      outer_jobs<HALF, false, RP, SZ, SP, GS, PL, OS>(a, h, p0, p1, u, un, 0, o);
     } else {
       // one tile of G pairs per wave
       const int q0 = p0 / GEO::G, q1 = (p1 + GEO::G - 1) / GEO::G;

@@ -842,6 +842,7 @@ struct Modes : Body<B, GEO, DT> {
       }
     }
   }
+  // (the OUTER pair loop below exists a second time, on blocked rows: dkf_os -- a change to one belongs in the other)
   template <bool HALF = false, bool RP = false>
   static FFC_FN void dkf(const DkfArgs& d, int h, int chunk, int wg_linear, int k0 = 0, int wv_in = 0) {
     const ConvArgs& a = d.c;
@@ -978,6 +979,67 @@ struct Modes : Body<B, GEO, DT> {
       }
       reduce_store_w(slab, u, wre, wim);
     }
+  }
+  // dkf on blocked rows (struct OsRows, ffc_conv_bwd_dkf_os): per pair of blocks W += FFT(dout window) conj(FFT(u window)).  The u window
+  // is the forward's (wrapped, o.wrap = 1: full-height phase A); the dout window holds the block's S samples and zeros above, so its
+  // phase A is the half-empty form and only half of its rows are loaded.  No gates.  Single-pass sizes with an outer digit.
+  // The unit setup, slab / scratch addressing and the four-phase loop are dkf's OUTER branch (single pass), kept as a function of its own so
+  // that dkf_kernel keeps its code and registers: a change to one loop belongs in the other.
+  static FFC_FN void dkf_os(const DkfArgs& d, const OsRows& o, int h, int chunk, int wg_linear) {
+    static_assert(GEO::OUTER, "blocked rows: sizes with an outer digit");
+    const ConvArgs& a = d.c;
+    BD::setup_tables(a.tab, a.t);
+    const int wv = B::wave();
+    Unit un;
+    un.wq = wv % GEO::NW;
+    const int u = wv / GEO::NW;
+    un.eb = u * GEO::EBYTES;
+    const int p0 = chunk * a.ppc;
+    int p1 = p0 + a.ppc;
+    if (p1 > a.npair) p1 = a.npair;
+    ConvArgs ad = a;
+    ad.u = d.dout; ad.sbu = d.sbd;
+    OsRows od = o;
+    od.wrap = 0;
+    float* slab = d.ws + ((int64_t)chunk * a.H + h) * (GEO::NT * 2048);
+    InnerRegs R;
+    const int iters = (p1 - p0 + GEO::UPW - 1) / GEO::UPW;
+    uint8_t* zs = (uint8_t*)d.zscratch + ((int64_t)(wg_linear * GEO::UPW + u)) * (GEO::N * 4);
+    WAcc W;
+    w_acc_zero(W);
+#pragma unroll 1
+    for (int it = 0; it < iters; it++) {
+      const int p = p0 + it * GEO::UPW + u;
+      const bool act = p < p1;
+      if (act) {
+        BD::template rows_in_os<BD::NCH>(a, o, h, p, un);
+        B::lds_fence();
+        BD::template outer_stage<true, false>(a.L, un, a.s_fwd);
+      }
+      BD::unit_barrier();
+      if (act) {
+        BD::template load_inner<false>(R, un);
+#pragma unroll 1
+        for (int tt = 0; tt < GEO::TPW; tt++) {
+          A16 re, im;
+          BD::template tile_fwd<false>(un.wq * GEO::TPW + tt, R, un, re, im);
+          z_store(zs, un.wq * GEO::TPW + tt, re, im, (a.flags & 4) != 0);
+        }
+      }
+      BD::unit_barrier();
+      if (act) {
+        BD::template rows_in_os<BD::NCH / 2>(ad, od, h, p, un);
+        B::lds_fence();
+        BD::template outer_stage<true, true>(a.L, un, a.s_fwd);
+      }
+      BD::unit_barrier();
+      if (act) {
+        BD::template load_inner<false>(R, un);
+        bwd_tiles<false, false>(a, h, un, R, zs, slab, it == 0, W, Pass());
+      }
+      BD::unit_barrier();
+    }
+    w_acc_finish(slab, u, un, W);
   }
   // ------------------------------------------------------------------ fused backward
   // per pair: Z_v = FFT(u*pregate); Z_d = FFT(dout*postgate); W += Z_d conj(Z_v);

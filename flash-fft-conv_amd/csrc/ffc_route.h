@@ -155,6 +155,41 @@ inline BwdRoute bwd_route(const DkfArgs& d, bool dkf) {
   return r;
 }
 
+// ---- overlap-save form on blocked rows (struct OsRows; conv_os_kernel and dkf_os_kernel): a row of L samples as nblk = ceil(L / S)
+// blocks of S = N / 2, the kernels' batch B * nblk.  Single-pass sizes with an outer digit: their window has a history half.
+struct OsRoute {
+  int grid, lds_max, lds;
+  const char* err;
+};
+static constexpr const char* NO_OS = "overlap-save form: fft 4096 / 8192 / 16384 / 32768, no gates";
+inline int64_t os_blocks(int64_t N, int64_t L) { return (L + N / 2 - 1) / (N / 2); }
+// The row copies index a tensor row in 32 bits up to one window past its end (j S + n < nblk S + S), and the batch of blocks is an int
+inline const char* os_limits(int64_t N, int64_t B, int64_t H, int64_t L) {
+  if (B * H * L >= ((int64_t)1 << 31) || L + N >= ((int64_t)1 << 31) || B * os_blocks(N, L) >= ((int64_t)1 << 30))
+    return "overlap-save form: B * H * L and L + fft size must be below 2^31, B * blocks below 2^30";
+  return nullptr;
+}
+static constexpr int OS_CHUNK_SEARCH = 4096;      // pairs up to which the forward launcher runs the chunk-length search of the plain forward
+// a.B = B * nblk, a.L = N; grid as the plain kernels of the size take it (fft 4096: persistent, one workgroup per CU)
+template <class GEO>
+inline OsRoute os_route(const ConvArgs& a, const OsRows& o) {
+  OsRoute r{};
+  if (!GEO::OUTER || a.R > 1 || GEO::N > 32768 || a.pregate || a.postgate || o.S != GEO::N / 2 || o.nblk < 1 || o.L > (int64_t)o.nblk * o.S) {
+    r.err = NO_OS;
+    return r;
+  }
+  r.grid = ((a.H + 7) & ~7) * a.nchunk;
+  if (GEO::NW == 1 && a.persist > 0 && r.grid > a.persist) r.grid = a.persist;
+  r.lds_max = r.lds = GEO::LDS_BYTES;
+  return r;
+}
+// what the two entry points fill alike: the kernels' batch and window, the tensor's strides and rows
+inline void set_os_rows(ConvArgs* a, OsRows* o, int64_t N, int64_t B, int64_t H, int64_t L, int wrap) {
+  o->S = (int)(N / 2); o->nblk = (int)os_blocks(N, L); o->L = (int)L; o->wrap = wrap;
+  a->B = (int)(B * o->nblk); a->H = (int)H; a->L = (int)N; a->npair = (a->B + 1) / 2;
+  a->sbu = a->sbg = a->sbp = a->sby = H * L;
+}
+
 // ---- frequency-sparse fused backward (bwd_sp_kernel, Modes::bwd_sp) and its dk_f -> dk kernel (dkifft_sp_kernel): refused where the
 // forward's sparse form is (fwd_route: GEO::HAS_SP, single pass, 1 <= rows <= 4, no spectrum buffer); one workgroup per (head, chunk)
 struct BwdSpRoute {

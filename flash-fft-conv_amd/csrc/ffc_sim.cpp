@@ -507,6 +507,27 @@ static int sim_bwd_t(const DkfArgs& d) {
     }
   }, r.multi_pass, r.half, r.fastk, !DKF && GEO::OUTER && !r.multi_pass && d.zin != nullptr);
 }
+// conv_os_kernel / dkf_os_kernel (ffc_k_conv_os.hip, ffc_k_dkf_os.hip)
+template <class GEO, int DT> struct ConvOsRun {
+  static int run(const ConvArgs& a, const OsRows& o) {
+    if (os_route<GEO>(a, o).err) return NO_KERNEL;
+    if constexpr (GEO::OUTER) {
+      return sim_jobs(a.H, a.nchunk, GEO::LDS_BYTES, [&](int h, int c) {
+        Body<SimB, GEO, DT>::setup_tables(a.tab, a.t);
+        Body<SimB, GEO, DT>::template conv_job<false, false, false, false, false, false, true>(a, h, c, o);
+      });
+    } else {
+      return NO_KERNEL;
+    }
+  }
+};
+template <class GEO, int DT> struct DkfOsRun {
+  static int run(const DkfArgs& d, const OsRows& o) {
+    if (os_route<GEO>(d.c, o).err) return NO_KERNEL;
+    if constexpr (GEO::OUTER) return sim_jobs(d.c.H, d.c.nchunk, GEO::LDS_BYTES, [&](int h, int c) { Modes<SimBO, GEO, DT>::dkf_os(d, o, h, c, h * d.c.nchunk + c); });
+    else return NO_KERNEL;
+  }
+};
 template <class GEO, int DT> struct DkfRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, true>(d); } };
 template <class GEO, int DT> struct BwdRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, false>(d); } };
 template <class GEO, int DT> struct DkRun {
@@ -968,6 +989,42 @@ int ffcsim_conv_bwd_dkf(int N, int dtype, const void* dout, const void* u, const
   d.zscratch = zs.data();
   int rc = dispatch<DkfRun>(N, dtype, d);
   return rc < 0 ? rc : a.nchunk;   // number of slabs written (one per chunk)
+}
+
+// The overlap-save form on blocked rows (ffc_conv_fwd_os / ffc_conv_bwd_dkf_os) on host memory, one chunk per head: the library's
+// rules (ffc_route.h set_os_rows / os_route) and the instantiations its kernels run.  ws as ffcsim_conv_bwd_dkf; returns the slab count.
+int ffcsim_conv_fwd_os(int N, int dtype, const void* u, const void* kf, void* y, int B, int H, int L, int conj_kf, int wrap) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (B <= 0 || H <= 0 || L <= 0 || os_limits(N, B, H, L)) return -2;
+  ConvArgs a{};
+  OsRows o{};
+  a.u = u; a.y = y; a.kf = kf; a.tab = p.blob.data(); a.t = p.tabs;
+  set_os_rows(&a, &o, N, B, H, L, wrap ? 1 : 0);
+  a.nchunk = 1; a.ppc = a.npair; a.conj_kf = conj_kf; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R;
+  a.flags = g_sim_flags;
+  return dispatch<ConvOsRun>(N, dtype, a, o);
+}
+int ffcsim_conv_bwd_dkf_os(int N, int dtype, const void* dout, const void* u, float* ws, int B, int H, int L) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (B <= 0 || H <= 0 || L <= 0 || os_limits(N, B, H, L)) return -2;
+  DkfArgs d{};
+  OsRows o{};
+  ConvArgs& a = d.c;
+  a.u = u; a.tab = p.blob.data(); a.t = p.tabs;
+  set_os_rows(&a, &o, N, B, H, L, 1);
+  d.sbd = d.sbdu = d.sbdpre = d.sbdpost = (int64_t)H * L;
+  a.nchunk = 1; a.ppc = a.npair; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R;
+  d.dout = dout; d.ws = ws;
+  std::vector<uint8_t> zs((size_t)H * ffcsim_upw(N) * N * 4 + 16);
+  d.zscratch = zs.data();
+  int rc = dispatch<DkfOsRun>(N, dtype, d, o);
+  return rc < 0 ? rc : a.nchunk;
 }
 
 // fused backward: du (and dpre if non-null) + dk_f slabs; returns the number of slabs

@@ -4,6 +4,7 @@ Same classes, constructor arguments and semantics as the reference's torch.fft d
 (/root/reference/flashfftconv/sparse_conv.py:8-38), but running through the fused HIP path:
 
   PartialFFTConv(N_partial)(x, k)          y = conv(x, k[..., :N_partial]),             fft size 2L
+  PartialFFTConv(N_partial, overlap_save=True)   the same y block by block for N_partial <= 16384: any L, blocks of max(2048, nextpow2(taps))
   FrequencySparseFFTConv(N_partial)(x, k)  y = irfft(rfft(x) * rfft(k) * [f < N_partial // 2]), fft size 2L
 
 x is (B, H, L) bf16/fp16 on the GPU, k is (H, Lk) fp32 (the reference demos up-cast x to fp32 and back;
@@ -14,6 +15,8 @@ fft 131072 the mask goes onto the inner k_f / dk_f rows of the HBM-level form, f
 """
 import torch
 
+from . import _lib
+from . import conv as _C
 from .conv import FlashFFTConv
 
 
@@ -39,11 +42,105 @@ class _ConvCache(torch.nn.Module):
         return conv
 
 
+OS_MAX_TAPS = 16384      # overlap-save route: the block fft size 2 * nextpow2(taps) stays a single-pass size with an outer digit (<= 32768)
+
+
+def os_fft_size(taps):
+    """block fft size N' of the overlap-save route for a filter of `taps` taps: blocks of S = N' / 2 samples, S >= taps"""
+    return max(4096, 2 * (1 << (taps - 1).bit_length()))
+
+
+def _conv_os(plan, x, kf, conj, wrap):
+    """ffc_conv_fwd_os on a contiguous (B, H, L) tensor: every row as ceil(L / S) blocks on the plan's fused kernel"""
+    B, H, L = x.shape
+    y = torch.empty_like(x)
+    _lib.check(_lib.lib().ffc_conv_fwd_os(plan.handle, _lib.ptr(x), _lib.ptr(kf), _lib.ptr(y), B, H, L, int(conj), int(wrap), _lib.stream_ptr()),
+               "ffc_conv_fwd_os")
+    return y
+
+
+def _dkf_os(plan, dy, x):
+    """ffc_conv_bwd_dkf_os: the fp32 dk_f partial sums over all blocks -> (the kernels' batch B * nblk, the workspace that holds them)"""
+    B, H, L = x.shape
+    nb = B * (-(-L // (plan.seqlen // 2)))
+    ws = torch.empty(_C._ws_bytes(plan, nb, H), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().ffc_conv_bwd_dkf_os(plan.handle, _lib.ptr(dy), _lib.ptr(x), _lib.ptr(ws), B, H, L, _lib.stream_ptr()), "ffc_conv_bwd_dkf_os")
+    return nb, ws
+
+
+class _OverlapSaveFn(torch.autograd.Function):
+    """y = conv(x, k) for k of at most S taps, block by block.  Keeps x and k_f only; the backward is the input-gradient launch (conj k_f on
+    the natural-order windows of dy), the dk_f launch over all B * nblk blocks and the dk inverse."""
+
+    @staticmethod
+    def forward(ctx, x, k, plan):
+        with torch.cuda.device(x.device):
+            kf = _C._kernel_fft(plan, k)
+            y = _conv_os(plan, x, kf, False, True)
+        ctx.save_for_backward(x, kf)
+        ctx.plan, ctx.k_shape, ctx.k_dtype = plan, tuple(k.shape), k.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kf = ctx.saved_tensors
+        plan, (H, Lk) = ctx.plan, ctx.k_shape
+        B, _, L = x.shape
+        dy = dy.contiguous()
+        dx = dk = None
+        with torch.cuda.device(x.device):
+            if ctx.needs_input_grad[0]:
+                dx = _conv_os(plan, dy, kf, True, False)
+            if ctx.needs_input_grad[1]:
+                nb, ws = _dkf_os(plan, dy, x)
+                dk = torch.empty(H, Lk, dtype=torch.float32, device=x.device)
+                _lib.check(_lib.lib().ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), nb, H, Lk, _lib.ptr(dk), _lib.stream_ptr()),
+                           "ffc_kernel_ifft_grad")
+                dk = dk.to(ctx.k_dtype)
+        return dx, dk, None
+
+
 class PartialFFTConv(_ConvCache):
-    """reference flashfftconv/sparse_conv.py:8-22"""
+    """reference flashfftconv/sparse_conv.py:8-22
+
+    overlap_save=True: a filter of P = min(N_partial, Lk) <= 16384 taps needs P - 1 samples of history, so every row is cut into blocks of
+    S = os_fft_size(P) / 2 samples and each block runs on the one-launch fused kernel of fft size 2 S with the previous block as its
+    history (ffc_conv_fwd_os): any sequence length, work per sample set by P and not by L, and nothing kept for the backward beyond x
+    and k_f.  Rows that fit one block (L <= S) keep the 2 L route where 2 L is a supported fft size, as do filters of more than 16384
+    taps.  On the blocked route `residual` is added by composition (y + residual), not inside the kernel."""
+
+    def __init__(self, N_partial, overlap_save=False):
+        super().__init__(N_partial)
+        self.overlap_save = overlap_save
+
+    def _os_plan(self, x, k):
+        """the block plan of the overlap-save route for this call, or None: today's 2 L route"""
+        if not self.overlap_save or not torch.is_tensor(x) or not torch.is_tensor(k) or x.dim() != 3 or k.dim() != 2:
+            return None
+        L, taps = x.shape[-1], min(self.N_partial, k.shape[-1])
+        if x.dtype not in (torch.bfloat16, torch.float16) or L < 1 or not 1 <= taps <= OS_MAX_TAPS:
+            return None
+        n = os_fft_size(taps)
+        if L <= n // 2 and 2 * L in _C.SUPPORTED_SEQLENS:
+            return None
+        if x.numel() >= 2 ** 31 or L + n >= 2 ** 31:      # (the kernels index a row in 32 bits up to one window past its end)
+            raise RuntimeError("PartialFFTConv: B * H * L and L + the block fft size must be below 2^31")
+        if not x.is_cuda:
+            raise RuntimeError("PartialFFTConv: x must be a CUDA/HIP tensor (no CPU fallback in the product path)")
+        if k.device != x.device:
+            raise RuntimeError(f"PartialFFTConv: k is on {k.device}, x on {x.device}")
+        if k.shape[0] != x.shape[1]:
+            raise RuntimeError(f"PartialFFTConv: k has {k.shape[0]} rows, x {x.shape[1]} heads")
+        return _C.get_plan(n, x.dtype, x.device)
 
     def forward(self, x, k, residual=None):
-        return self._conv_for(x)(x, k[..., : self.N_partial], residual=residual)
+        plan = self._os_plan(x, k)
+        if plan is None:
+            return self._conv_for(x)(x, k[..., : self.N_partial], residual=residual)
+        if residual is not None:
+            _C._check_residual(x, residual)
+        y = _OverlapSaveFn.apply(x.contiguous(), k[..., : self.N_partial], plan)
+        return y if residual is None else y + residual
 
 
 class FrequencySparseFFTConv(_ConvCache):

@@ -79,6 +79,20 @@ int64_t ffc_dkf_workspace_bytes(const ffc_plan* plan, int64_t B, int64_t H);
 int64_t ffc_dkf_slab_count(const ffc_plan* plan, int64_t B, int64_t H);
 int ffc_conv_bwd_dkf(const ffc_plan* plan, const void* dout, const void* u, const void* pregate, const void* postgate,
                      void* ws, int64_t B, int64_t H, int64_t L, void* stream);
+/* Overlap-save form of ffc_conv_fwd / ffc_conv_bwd_dkf for SHORT filters on rows of ANY length L (PartialFFTConv(overlap_save=True);
+ * the reference's partial convolution pays a 2L-point transform, flashfftconv/sparse_conv.py:8-22).  plan: fft size N' in 4096 ... 32768
+ * whose k_f holds a filter of at most S = N' / 2 taps (ffc_kernel_fft with Lk <= S).  Every row is cut into nblk = ceil(L / S) blocks;
+ * block j is one N'-point circular convolution whose window holds the block at positions n < S and, with wrap = 1, the PREVIOUS block
+ * at n >= S (the circular negative lags), wrap = 0: samples j S + n in natural order; zero outside [0, L).  Window outputs n < S are
+ * y[b, h, j S + n]: exact, nothing wraps.  wrap = 1, conj_kf = 0: y = conv(u, k).  wrap = 0, conj_kf = 1 on dy: the input gradient
+ * (no overlap-add).  u, y contiguous (B, H, L) of the plan dtype, no gates; 16-byte accesses when L % 8 == 0.  The kernels' batch is
+ * B * nblk: work per sample depends on N', not on L.  u and y must be DISTINCT buffers: block j + 1 reads block j of u as its history,
+ * possibly in another workgroup and after block j's outputs are stored.  B * H * L < 2^31, L + N' < 2^31 and B * nblk < 2^30. */
+int ffc_conv_fwd_os(const ffc_plan* plan, const void* u, const void* kf, void* y, int64_t B, int64_t H, int64_t L, int conj_kf,
+                    int wrap, void* stream);
+/* dk_f partial sums over all B * nblk blocks: window of u as ffc_conv_fwd_os(wrap = 1) takes it, window of dout = the block's S samples
+ * and zeros above.  ws: ffc_dkf_workspace_bytes(plan, B * nblk, H) bytes; finish with ffc_kernel_ifft_grad(plan, ws, B * nblk, H, Lk, ..). */
+int ffc_conv_bwd_dkf_os(const ffc_plan* plan, const void* dout, const void* u, void* ws, int64_t B, int64_t H, int64_t L, void* stream);
 /* Fused backward (one launch): du = pregate * corr(dout*postgate, k), dpre = u * corr(...) (nullable) and the
  * dk_f partial sums in ws.  Covers monarch_conv_backward{,_r2r,_16_16_16,...} (monarch.cpp:27-32): three
  * transforms per pair like the reference's bwd kernels, dk_f kept in fp32. */
