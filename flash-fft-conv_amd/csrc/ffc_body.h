@@ -91,6 +91,17 @@ struct ConvArgs {
 struct OsRows {
   int nblk, S, L, wrap;
 };
+// Gated form of the blocked rows (ffc_conv_fwd_os_gated / ffc_conv_bwd_dkf_os_gated; kernels of their own, the ungated ones read none of
+// this).  Every operand is a (B, H, L) tensor of the module dtype, nullable, with a batch stride of its own, and is read at the sample's
+// own source index:
+//   in   window = u * ConvArgs::pregate (sbg), fp32 product rounded once before the LDS write (rows_in_os_g)
+//   out  y = raw * ConvArgs::postgate (sbp) + ConvArgs::addend (sba), fp32 product and sum, one rounding; and from the same registers the
+//        second output out2 = raw * gate2 (rows_out_os_g).  The input gradient is dx = g * pregate with dpregate = g * x as out2.
+struct OsGate {
+  const void* gate2;
+  void* out2;
+  int64_t sbg2, sbo2;
+};
 
 // One pass of a multi-pass size (fft size N = R * M, M = GEO::N = N1 * Mi; HostPlan::R).  With n = n0 M + n1 Mi + mi and
 // f = k0 + R f', pass k0 computes the M-point circular convolution of
@@ -1056,6 +1067,134 @@ struct Body {
         v.z = B::sel(sw, w.x, w.z); v.w = B::sel(sw, w.y, w.w);
         // (gstore8's predicate is `position < L` of the tensor row: the ragged last block ends there)
         gstore8((uint16_t*)a.y + P[pl].ro, row * GEO::Mi + m + P[pl].s0, o.L, fast, P[pl].ok, v);
+      }
+    }
+  }
+  // ---- gated form (struct OsGate).  Gates, addend and the second output are tensors of the sample's shape, so each is addressed by the
+  // OsPlane of its own batch stride and the chunk scalars of the sample (os_s0 / os_dead).  Which operands exist is a wave-uniform
+  // null-pointer test inside kernels that are only launched with at least one of them.
+  // 8 samples of window position n (first row of the chunk at r0) from source index n + s0: rows_load_os's two arms.  16-byte arm: the
+  // clamped position lies inside the tensor row for any operand (a dead chunk reads from the row's start); element-wise: per-element `< L`.
+  static FFC_FN U4 os_load8(const uint16_t* base, i32 n, int s0, int r0, bool dead, int L, int fast) {
+    if (fast) {
+      const i32 n16 = B::imin(n + (dead ? -r0 : s0), L - 8) >> 3;
+      return fast == 2 ? B::g_r128_nt(base, n16) : B::g_r128(base, n16);
+    }
+    u32 w[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const i32 e0 = n + (s0 + 2 * q), e1 = n + (s0 + 2 * q + 1);
+      u32 lo = B::g_r16(base, e0, (e0 < L) && !dead);
+      u32 hi = B::g_r16(base, e1, (e1 < L) && !dead);
+      w[q] = lo | (hi << 16);
+    }
+    U4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    return v;
+  }
+  // window of u * pregate -> E.  The loads of GB chunks (both planes, sample and gate) are issued together ahead of the work on them, as
+  // rows_store_g does; GB is the caller's register budget (forward 4, dk_f kernel 2).  Zeroing outside [0, L) stays at the LDS write.
+  template <int NC, int GB>
+  static FFC_FN void rows_in_os_g(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un) {
+    static_assert(GEO::OUTER && NC % GB == 0, "blocked rows: sizes with an outer digit; whole gate batches");
+    const i32 lane = B::opaque(B::lane());
+    const int fast = a.fast ? (a.stream ? 2 : 1) : 0;
+    const bool hasg = a.pregate != nullptr;
+    const OsPlane P[2] = {os_plane(a, o, a.sbu, h, pq, 0), os_plane(a, o, a.sbu, h, pq, 1)};
+    const OsPlane PG[2] = {os_plane(a, o, a.sbg, h, pq, 0), os_plane(a, o, a.sbg, h, pq, 1)};
+#pragma unroll
+    for (int ib = 0; ib < NC; ib += GB) {
+      U4 X[GB][2], G[GB][2];
+#pragma unroll
+      for (int jj = 0; jj < GB; jj++) {
+        const int i = ib + jj, r0 = ((i * 64) / CPR) * GEO::Mi;
+        i32 idx = lane + i * 64;
+        i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+        const i32 n = row * GEO::Mi + m;
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++) {
+          const int s0 = os_s0(o, P[pl], i, true);
+          const bool dead = os_dead(o, P[pl], i, s0);
+          X[jj][pl] = os_load8((const uint16_t*)a.u + P[pl].ro, n, s0, r0, dead, o.L, fast);
+          if (hasg) G[jj][pl] = os_load8((const uint16_t*)a.pregate + PG[pl].ro, n, s0, r0, dead, o.L, fast);
+        }
+      }
+      B::sched_fence();
+#pragma unroll
+      for (int jj = 0; jj < GB; jj++) {
+        const int i = ib + jj;
+        i32 idx = lane + i * 64;
+        i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+        pred sw;
+        i32 off = pair_off(row, m, &sw) + un.eb;
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++) {
+          const int s0 = os_s0(o, P[pl], i, true);
+          pred ok = ((row * GEO::Mi + m + s0) < o.L) && !os_dead(o, P[pl], i, s0);
+          U4 v = X[jj][pl];
+          if (hasg) v = mul4(v, G[jj][pl]);
+          v = mask4(v, ok);
+          U4 w;
+          w.x = B::sel(sw, v.z, v.x); w.y = B::sel(sw, v.w, v.y);
+          w.z = B::sel(sw, v.x, v.z); w.w = B::sel(sw, v.y, v.w);
+          B::lds_w128(off + pl * GEO::PLANE, w, B::ptrue());
+        }
+      }
+    }
+  }
+  // window positions n < S of E -> y = raw * postgate + addend, and out2 = raw * gate2, at samples j S + n < L.  The loads of a batch of
+  // chunks first, as rows_out_g; a plane that does not exist (odd batch) reads from the start of row (0, h) and stores nothing.
+  template <int GB>
+  static FFC_FN void rows_out_os_g(const ConvArgs& a, const OsRows& o, const OsGate& g, int h, int pq, Unit un) {
+    static_assert((NCH / 2) % GB == 0, "whole gate batches");
+    const i32 lane = B::opaque(B::lane());
+    const int fast = a.fast ? (a.stream ? 2 : 1) : 0;
+    const bool hasg = a.postgate != nullptr, hasr = a.addend != nullptr, has2 = g.out2 != nullptr;
+    OsPlane PY[2], PG[2], PR[2], P2[2], PO[2];
+#pragma unroll
+    for (int pl = 0; pl < 2; pl++) {
+      PY[pl] = os_plane(a, o, a.sby, h, pq, pl); PG[pl] = os_plane(a, o, a.sbp, h, pq, pl); PR[pl] = os_plane(a, o, a.sba, h, pq, pl);
+      P2[pl] = os_plane(a, o, g.sbg2, h, pq, pl); PO[pl] = os_plane(a, o, g.sbo2, h, pq, pl);
+    }
+#pragma unroll
+    for (int ib = 0; ib < NCH / 2; ib += GB) {
+      U4 G[GB][2], Rr[GB][2], G2[GB][2];
+#pragma unroll
+      for (int jj = 0; jj < GB; jj++) {
+        const int i = ib + jj, r0 = ((i * 64) / CPR) * GEO::Mi;
+        i32 idx = lane + i * 64;
+        i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+        const i32 n = row * GEO::Mi + m;
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++) {
+          // (the block's start j S lies inside the row, so only its ragged end is clamped or predicated away)
+          const int s0 = PY[pl].s0;
+          const bool dead = !PY[pl].ok || s0 + r0 >= o.L;
+          if (hasg) G[jj][pl] = os_load8((const uint16_t*)a.postgate + PG[pl].ro, n, s0, r0, dead, o.L, fast);
+          if (hasr) Rr[jj][pl] = os_load8((const uint16_t*)a.addend + PR[pl].ro, n, s0, r0, dead, o.L, fast);
+          if (has2) G2[jj][pl] = os_load8((const uint16_t*)g.gate2 + P2[pl].ro, n, s0, r0, dead, o.L, fast);
+        }
+      }
+      B::sched_fence();
+#pragma unroll
+      for (int jj = 0; jj < GB; jj++) {
+        const int i = ib + jj;
+        i32 idx = lane + i * 64;
+        i32 row = idx / CPR, m = (idx % CPR) * 8 + un.wq * 128 * GEO::S1;
+        pred sw;
+        i32 off = pair_off(row, m, &sw) + un.eb;
+#pragma unroll
+        for (int pl = 0; pl < 2; pl++) {
+          U4 w = B::lds_r128(off + pl * GEO::PLANE);
+          U4 v;
+          v.x = B::sel(sw, w.z, w.x); v.y = B::sel(sw, w.w, w.y);
+          v.z = B::sel(sw, w.x, w.z); v.w = B::sel(sw, w.y, w.w);
+          const i32 n = row * GEO::Mi + m + PY[pl].s0;
+          if (has2) gstore8((uint16_t*)g.out2 + PO[pl].ro, n, o.L, fast, PY[pl].ok, mul4(v, G2[jj][pl]));
+          if (hasg && hasr) v = fma4(v, G[jj][pl], Rr[jj][pl]);
+          else if (hasg) v = mul4(v, G[jj][pl]);
+          else if (hasr) v = sum4(v, Rr[jj][pl]);
+          gstore8((uint16_t*)a.y + PY[pl].ro, n, o.L, fast, PY[pl].ok, v);
+        }
       }
     }
   }
@@ -2568,8 +2707,11 @@ struct Body {
   // PL: the input rows are plain too (ffc::plain_rows_ok): rows_load_pl / rows_store_pl, no gate, side-product or element-wise arm
   // OS: blocked rows (struct OsRows `o`): the whole window comes in (rows_load_os / rows_store_os, full-height phase A) and only the
   //     window positions n < S go out, so phase C runs its half-height form and rows_out_os moves half of the rows
-  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false>
-  static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0, OsRows o = OsRows()) {
+  // OSG: the gated form of OS (struct OsGate `og`): rows_in_os_g / rows_out_os_g, a kernel of its own
+  template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false,
+            bool OSG = false>
+  static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0, OsRows o = OsRows(), OsGate og = OsGate()) {
+    static_assert(!OSG || OS, "gated blocked rows: a form of the blocked-row kernel");
     static_assert(!GS || (HALF && !RP && !SP && HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
     static_assert(!PL || GS, "plain input rows: a form of the direct-store kernels");
     static_assert(!OS || !(HALF || PROF || RP || SZ || SP || GS || PL), "blocked rows: a form of the plain full-length kernel");
@@ -2635,7 +2777,9 @@ struct Body {
         if constexpr (RP) {
           rows_in_rp<NC>(a, h, p, un, ps);
         } else if constexpr (!ROT) {
-          if constexpr (OS) {
+          if constexpr (OSG) {
+            rows_in_os_g<NC, 4>(a, o, h, p, un);
+          } else if constexpr (OS) {
             rows_load_os<NC>(a, o, h, p, un, X);
             rows_store_os<NC>(a, o, h, p, un, X);
           } else {
@@ -2736,7 +2880,8 @@ struct Body {
             else rows_out<NC, false>(ar, h, p, un);
           }
         }
-        if constexpr (OS) rows_out_os(a, o, h, p, un);
+        if constexpr (OSG) rows_out_os_g<4>(a, o, og, h, p, un);
+        else if constexpr (OS) rows_out_os(a, o, h, p, un);
         else if constexpr (RP) rows_out_rp<NC>(a, h, p, un, ps);
         else rows_out<NC>(a, h, p, un);
         FFC_TICK(6)
@@ -2761,8 +2906,8 @@ struct Body {
     conv_job<HALF, false, SZ, SP, GS, PL>(a, h, chunk);
   }
   // one (head, chunk) job; the tables are already in LDS.  RP: all passes of a multi-pass size
-  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false>
-  static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk, OsRows o = OsRows()) {
+  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false, bool OSG = false>
+  static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk, OsRows o = OsRows(), OsGate og = OsGate()) {
     const int wv = B::wave();
     Unit un;
     un.wq = wv % GEO::NW;
@@ -2772,7 +2917,7 @@ struct Body {
     int p1 = p0 + a.ppc;
     if (p1 > a.npair) p1 = a.npair;
     if constexpr (GEO::OUTER) {
-      outer_jobs<HALF, false, RP, SZ, SP, GS, PL, OS>(a, h, p0, p1, u, un, 0, o);
+      outer_jobs<HALF, false, RP, SZ, SP, GS, PL, OS, OSG>(a, h, p0, p1, u, un, 0, o, og);
     } else {
       // one tile of G pairs per wave
       const int q0 = p0 / GEO::G, q1 = (p1 + GEO::G - 1) / GEO::G;

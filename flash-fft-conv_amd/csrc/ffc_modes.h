@@ -982,9 +982,12 @@ struct Modes : Body<B, GEO, DT> {
   }
   // dkf on blocked rows (struct OsRows, ffc_conv_bwd_dkf_os): per pair of blocks W += FFT(dout window) conj(FFT(u window)).  The u window
   // is the forward's (wrapped, o.wrap = 1: full-height phase A); the dout window holds the block's S samples and zeros above, so its
-  // phase A is the half-empty form and only half of its rows are loaded.  No gates.  Single-pass sizes with an outer digit.
+  // phase A is the half-empty form and only half of its rows are loaded.  Single-pass sizes with an outer digit.
   // The unit setup, slab / scratch addressing and the four-phase loop are dkf's OUTER branch (single pass), kept as a function of its own so
   // that dkf_kernel keeps its code and registers: a change to one loop belongs in the other.
+  // G (ffc_conv_bwd_dkf_os_gated, a kernel of its own): the wrapped window is of u * pregate, the S-sample window of dout * postgate
+  // (Body::rows_in_os_g, two chunks of loads in flight: the 128-register budget).
+  template <bool G = false>
   static FFC_FN void dkf_os(const DkfArgs& d, const OsRows& o, int h, int chunk, int wg_linear) {
     static_assert(GEO::OUTER, "blocked rows: sizes with an outer digit");
     const ConvArgs& a = d.c;
@@ -999,6 +1002,7 @@ struct Modes : Body<B, GEO, DT> {
     if (p1 > a.npair) p1 = a.npair;
     ConvArgs ad = a;
     ad.u = d.dout; ad.sbu = d.sbd;
+    if constexpr (G) { ad.pregate = a.postgate; ad.sbg = a.sbp; }
     OsRows od = o;
     od.wrap = 0;
     float* slab = d.ws + ((int64_t)chunk * a.H + h) * (GEO::NT * 2048);
@@ -1012,7 +1016,8 @@ struct Modes : Body<B, GEO, DT> {
       const int p = p0 + it * GEO::UPW + u;
       const bool act = p < p1;
       if (act) {
-        BD::template rows_in_os<BD::NCH>(a, o, h, p, un);
+        if constexpr (G) BD::template rows_in_os_g<BD::NCH, 2>(a, o, h, p, un);
+        else BD::template rows_in_os<BD::NCH>(a, o, h, p, un);
         B::lds_fence();
         BD::template outer_stage<true, false>(a.L, un, a.s_fwd);
       }
@@ -1028,7 +1033,8 @@ struct Modes : Body<B, GEO, DT> {
       }
       BD::unit_barrier();
       if (act) {
-        BD::template rows_in_os<BD::NCH / 2>(ad, od, h, p, un);
+        if constexpr (G) BD::template rows_in_os_g<BD::NCH / 2, 2>(ad, od, h, p, un);
+        else BD::template rows_in_os<BD::NCH / 2>(ad, od, h, p, un);
         B::lds_fence();
         BD::template outer_stage<true, true>(a.L, un, a.s_fwd);
       }

@@ -190,6 +190,45 @@ inline void set_os_rows(ConvArgs* a, OsRows* o, int64_t N, int64_t B, int64_t H,
   a->sbu = a->sbg = a->sbp = a->sby = H * L;
 }
 
+// ---- gated form of the blocked rows (struct OsGate; conv_os_g_kernel and dkf_os_g_kernel): the grid and LDS of os_route, gates allowed.
+// Every operand is optional (a call with none computes what the ungated kernels compute); a second output needs its gate.
+static constexpr const char* NO_OS_GATED = "gated overlap-save form: fft 4096 / 8192 / 16384 / 32768, a second output only with its gate";
+template <class GEO>
+inline OsRoute os_gated_route(const ConvArgs& a, const OsRows& o, const OsGate& g) {
+  ConvArgs plain = a;
+  plain.pregate = plain.postgate = nullptr;
+  OsRoute r = os_route<GEO>(plain, o);
+  if (r.err || (g.out2 && !g.gate2)) r.err = NO_OS_GATED;
+  return r;
+}
+// A block is its successor's history and a gate is read by the block's own workgroup only, so no output may share memory with any input
+// of the launch, nor with the other output: tensors of `elems` 16-bit elements; null pointers take no part.
+inline const char* os_alias(const void* const* outs, int nout, const void* const* ins, int nin, int64_t elems) {
+  const uintptr_t bytes = (uintptr_t)elems * 2;
+  for (int i = 0; i < nout; i++) {
+    if (!outs[i]) continue;
+    const uintptr_t w = (uintptr_t)outs[i];
+    for (int j = 0; j < nin + nout; j++) {
+      const void* q = j < nin ? ins[j] : outs[j - nin];
+      if (!q || (j >= nin && j - nin == i)) continue;
+      const uintptr_t r = (uintptr_t)q;
+      if (w < r + bytes && r < w + bytes) return "gated overlap-save form: an output overlaps an input or the other output of the launch";
+    }
+  }
+  return nullptr;
+}
+// the operands' batch strides for contiguous tensors (set_os_rows fills sbu / sbg / sbp / sby)
+inline void set_os_gate(ConvArgs* a, OsGate* g, const void* addend, const void* gate2, void* out2, int64_t H, int64_t L) {
+  a->addend = addend; a->sba = H * L;
+  g->gate2 = gate2; g->out2 = out2; g->sbg2 = g->sbo2 = H * L;
+}
+// 16-byte accesses: L % 8 == 0 and every tensor of the launch 16-byte aligned
+inline int os_fast(int64_t L, const void* const* ptrs, int n) {
+  uintptr_t all = 0;
+  for (int i = 0; i < n; i++) all |= (uintptr_t)ptrs[i];
+  return (L % 8 == 0) && !(all & 15);
+}
+
 // ---- frequency-sparse fused backward (bwd_sp_kernel, Modes::bwd_sp) and its dk_f -> dk kernel (dkifft_sp_kernel): refused where the
 // forward's sparse form is (fwd_route: GEO::HAS_SP, single pass, 1 <= rows <= 4, no spectrum buffer); one workgroup per (head, chunk)
 struct BwdSpRoute {

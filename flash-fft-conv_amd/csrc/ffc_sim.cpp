@@ -528,6 +528,30 @@ template <class GEO, int DT> struct DkfOsRun {
     else return NO_KERNEL;
   }
 };
+// conv_os_g_kernel / dkf_os_g_kernel (ffc_k_conv_os_g.hip, ffc_k_dkf_os_g.hip)
+template <class GEO, int DT> struct ConvOsGRun {
+  static int run(const ConvArgs& a, const OsRows& o, const OsGate& g) {
+    if (os_gated_route<GEO>(a, o, g).err) return NO_KERNEL;
+    if constexpr (GEO::OUTER) {
+      return sim_jobs(a.H, a.nchunk, GEO::LDS_BYTES, [&](int h, int c) {
+        Body<SimB, GEO, DT>::setup_tables(a.tab, a.t);
+        Body<SimB, GEO, DT>::template conv_job<false, false, false, false, false, false, true, true>(a, h, c, o, g);
+      });
+    } else {
+      return NO_KERNEL;
+    }
+  }
+};
+template <class GEO, int DT> struct DkfOsGRun {
+  static int run(const DkfArgs& d, const OsRows& o) {
+    if (os_gated_route<GEO>(d.c, o, OsGate()).err) return NO_KERNEL;
+    if constexpr (GEO::OUTER) {
+      return sim_jobs(d.c.H, d.c.nchunk, GEO::LDS_BYTES, [&](int h, int c) { Modes<SimBO, GEO, DT>::template dkf_os<true>(d, o, h, c, h * d.c.nchunk + c); });
+    } else {
+      return NO_KERNEL;
+    }
+  }
+};
 template <class GEO, int DT> struct DkfRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, true>(d); } };
 template <class GEO, int DT> struct BwdRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, false>(d); } };
 template <class GEO, int DT> struct DkRun {
@@ -1024,6 +1048,48 @@ int ffcsim_conv_bwd_dkf_os(int N, int dtype, const void* dout, const void* u, fl
   std::vector<uint8_t> zs((size_t)H * ffcsim_upw(N) * N * 4 + 16);
   d.zscratch = zs.data();
   int rc = dispatch<DkfOsRun>(N, dtype, d, o);
+  return rc < 0 ? rc : a.nchunk;
+}
+// The gated form (ffc_conv_fwd_os_gated / ffc_conv_bwd_dkf_os_gated), same rules (os_gated_route, os_alias, set_os_gate); -3: an output
+// overlaps an input
+int ffcsim_conv_fwd_os_gated(int N, int dtype, const void* u, const void* kf, const void* pregate, const void* postgate, const void* addend,
+                             void* y, const void* gate2, void* out2, int B, int H, int L, int conj_kf, int wrap) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (B <= 0 || H <= 0 || L <= 0 || os_limits(N, B, H, L)) return -2;
+  const void* const outs[] = {y, out2};
+  const void* const ins[] = {u, pregate, postgate, addend, gate2};
+  if (os_alias(outs, 2, ins, 5, (int64_t)B * H * L)) return -3;
+  ConvArgs a{};
+  OsRows o{};
+  OsGate g{};
+  a.u = u; a.y = y; a.kf = kf; a.pregate = pregate; a.postgate = postgate; a.tab = p.blob.data(); a.t = p.tabs;
+  set_os_rows(&a, &o, N, B, H, L, wrap ? 1 : 0);
+  set_os_gate(&a, &g, addend, gate2, out2, H, L);
+  a.nchunk = 1; a.ppc = a.npair; a.conj_kf = conj_kf; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R;
+  a.flags = g_sim_flags;
+  return dispatch<ConvOsGRun>(N, dtype, a, o, g);
+}
+int ffcsim_conv_bwd_dkf_os_gated(int N, int dtype, const void* dout, const void* u, const void* pregate, const void* postgate, float* ws,
+                                 int B, int H, int L) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (B <= 0 || H <= 0 || L <= 0 || os_limits(N, B, H, L)) return -2;
+  DkfArgs d{};
+  OsRows o{};
+  ConvArgs& a = d.c;
+  a.u = u; a.pregate = pregate; a.postgate = postgate; a.tab = p.blob.data(); a.t = p.tabs;
+  set_os_rows(&a, &o, N, B, H, L, 1);
+  d.sbd = d.sbdu = d.sbdpre = d.sbdpost = (int64_t)H * L;
+  a.nchunk = 1; a.ppc = a.npair; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R;
+  d.dout = dout; d.ws = ws;
+  std::vector<uint8_t> zs((size_t)H * ffcsim_upw(N) * N * 4 + 16);
+  d.zscratch = zs.data();
+  int rc = dispatch<DkfOsGRun>(N, dtype, d, o);
   return rc < 0 ? rc : a.nchunk;
 }
 

@@ -5,6 +5,7 @@ Same classes, constructor arguments and semantics as the reference's torch.fft d
 
   PartialFFTConv(N_partial)(x, k)          y = conv(x, k[..., :N_partial]),             fft size 2L
   PartialFFTConv(N_partial, overlap_save=True)   the same y block by block for N_partial <= 16384: any L, blocks of max(2048, nextpow2(taps))
+  PartialFFTConv(..)(x, k, pregate, postgate, residual)   y = postgate * conv(x * pregate, k[..., :N_partial]) + residual, each optional
   FrequencySparseFFTConv(N_partial)(x, k)  y = irfft(rfft(x) * rfft(k) * [f < N_partial // 2]), fft size 2L
 
 x is (B, H, L) bf16/fp16 on the GPU, k is (H, Lk) fp32 (the reference demos up-cast x to fp32 and back;
@@ -100,6 +101,74 @@ class _OverlapSaveFn(torch.autograd.Function):
         return dx, dk, None
 
 
+def _conv_os_gated(plan, x, kf, conj, wrap, pregate=None, postgate=None, addend=None, gate2=None):
+    """ffc_conv_fwd_os_gated on contiguous (B, H, L) tensors: y = postgate * conv_os(x * pregate) + addend and, with gate2, the second
+    output conv_os(x * pregate) * gate2 of the same launch -> (y, out2 or None)"""
+    B, H, L = x.shape
+    y = torch.empty_like(x)
+    out2 = None if gate2 is None else torch.empty_like(x)
+    _lib.check(_lib.lib().ffc_conv_fwd_os_gated(plan.handle, _lib.ptr(x), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(addend),
+                                                _lib.ptr(y), _lib.ptr(gate2), _lib.ptr(out2), B, H, L, int(conj), int(wrap), _lib.stream_ptr()),
+               "ffc_conv_fwd_os_gated")
+    return y, out2
+
+
+def _dkf_os_gated(plan, dy, x, pregate, postgate):
+    """ffc_conv_bwd_dkf_os_gated: the dk_f partial sums of the windows of x * pregate and dy * postgate -> (B * nblk, workspace)"""
+    B, H, L = x.shape
+    nb = B * (-(-L // (plan.seqlen // 2)))
+    ws = torch.empty(_C._ws_bytes(plan, nb, H), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().ffc_conv_bwd_dkf_os_gated(plan.handle, _lib.ptr(dy), _lib.ptr(x), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(ws),
+                                                    B, H, L, _lib.stream_ptr()), "ffc_conv_bwd_dkf_os_gated")
+    return nb, ws
+
+
+class _OverlapSaveGatedFn(torch.autograd.Function):
+    """y = postgate * conv(x * pregate, k) + residual block by block, every gate and the residual optional and inside the convolution
+    launch.  Keeps x, the gates and k_f.  The backward runs, each only where its gradient is asked for: the input-gradient launch (window
+    of dy * postgate, conj k_f; dx = g * pregate and dpregate = g * x from the same launch), the forward launch again with dy in the
+    postgate slot (dpostgate), and the gated dk_f launch with the dk inverse.  residual receives dy."""
+
+    @staticmethod
+    def forward(ctx, x, k, pregate, postgate, residual, plan):
+        with torch.cuda.device(x.device):
+            kf = _C._kernel_fft(plan, k)
+            y, _ = _conv_os_gated(plan, x, kf, False, True, pregate, postgate, residual)
+        ctx.save_for_backward(x, kf, pregate, postgate)
+        ctx.plan, ctx.k_shape, ctx.k_dtype = plan, tuple(k.shape), k.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kf, pregate, postgate = ctx.saved_tensors
+        plan, (H, Lk) = ctx.plan, ctx.k_shape
+        need = ctx.needs_input_grad
+        dy = dy.contiguous()
+        dx = dk = dpre = dpost = None
+        with torch.cuda.device(x.device):
+            want_dpre = need[2] and pregate is not None
+            if need[0] or want_dpre:
+                dx, dpre = _conv_os_gated(plan, dy, kf, True, False, postgate, pregate, None, x if want_dpre else None)
+            if need[3] and postgate is not None:
+                dpost, _ = _conv_os_gated(plan, x, kf, False, True, pregate, dy)
+            if need[1]:
+                nb, ws = _dkf_os_gated(plan, dy, x, pregate, postgate)
+                dk = torch.empty(H, Lk, dtype=torch.float32, device=x.device)
+                _lib.check(_lib.lib().ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), nb, H, Lk, _lib.ptr(dk), _lib.stream_ptr()),
+                           "ffc_kernel_ifft_grad")
+                dk = dk.to(ctx.k_dtype)
+        return dx if need[0] else None, dk, dpre, dpost, dy if need[4] else None, None
+
+
+def _check_gate(x, name, g):
+    if not torch.is_tensor(g):
+        raise RuntimeError(f"PartialFFTConv: {name} must be a tensor")
+    if g.device != x.device:
+        raise RuntimeError(f"PartialFFTConv: {name} is on {g.device}, x on {x.device}")
+    if g.shape != x.shape or g.dtype != x.dtype:
+        raise RuntimeError(f"PartialFFTConv: {name} must match x in shape and dtype")
+
+
 class PartialFFTConv(_ConvCache):
     """reference flashfftconv/sparse_conv.py:8-22
 
@@ -107,7 +176,7 @@ class PartialFFTConv(_ConvCache):
     S = os_fft_size(P) / 2 samples and each block runs on the one-launch fused kernel of fft size 2 S with the previous block as its
     history (ffc_conv_fwd_os): any sequence length, work per sample set by P and not by L, and nothing kept for the backward beyond x
     and k_f.  Rows that fit one block (L <= S) keep the 2 L route where 2 L is a supported fft size, as do filters of more than 16384
-    taps.  On the blocked route `residual` is added by composition (y + residual), not inside the kernel."""
+    taps.  Gates and `residual` are fused into the blocked launches as well (ffc_conv_fwd_os_gated, ffc_conv_bwd_dkf_os_gated): see forward."""
 
     def __init__(self, N_partial, overlap_save=False):
         super().__init__(N_partial)
@@ -133,14 +202,26 @@ class PartialFFTConv(_ConvCache):
             raise RuntimeError(f"PartialFFTConv: k has {k.shape[0]} rows, x {x.shape[1]} heads")
         return _C.get_plan(n, x.dtype, x.device)
 
-    def forward(self, x, k, residual=None):
+    def forward(self, x, k, pregate=None, postgate=None, residual=None):
+        """y = postgate * conv(x * pregate, k[..., :N_partial]) + residual; each of pregate, postgate, residual (x's shape, dtype and device)
+        is optional on its own.  Differentiable in x, k and the gates; residual receives the incoming gradient.  On the blocked route a
+        call with a gate or a residual keeps x, the gates and k_f for the backward (no spectra, no output before the gate) and recomputes
+        the forward once where dpostgate is asked for; a call with neither keeps x and k_f."""
         plan = self._os_plan(x, k)
         if plan is None:
-            return self._conv_for(x)(x, k[..., : self.N_partial], residual=residual)
+            if (pregate is None) != (postgate is None):      # FlashFFTConv takes both gates or none: the missing one is all ones
+                ones = torch.ones_like(pregate if postgate is None else postgate)
+                pregate, postgate = (ones if pregate is None else pregate), (ones if postgate is None else postgate)
+            return self._conv_for(x)(x, k[..., : self.N_partial], pregate, postgate, residual=residual)
+        if pregate is None and postgate is None and residual is None:
+            return _OverlapSaveFn.apply(x.contiguous(), k[..., : self.N_partial], plan)
+        for name, g in (("pregate", pregate), ("postgate", postgate)):
+            if g is not None:
+                _check_gate(x, name, g)
         if residual is not None:
             _C._check_residual(x, residual)
-        y = _OverlapSaveFn.apply(x.contiguous(), k[..., : self.N_partial], plan)
-        return y if residual is None else y + residual
+        pregate, postgate, residual = (None if t is None else t.contiguous() for t in (pregate, postgate, residual))
+        return _OverlapSaveGatedFn.apply(x.contiguous(), k[..., : self.N_partial], pregate, postgate, residual, plan)
 
 
 class FrequencySparseFFTConv(_ConvCache):

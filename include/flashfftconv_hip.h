@@ -93,6 +93,20 @@ int ffc_conv_fwd_os(const ffc_plan* plan, const void* u, const void* kf, void* y
 /* dk_f partial sums over all B * nblk blocks: window of u as ffc_conv_fwd_os(wrap = 1) takes it, window of dout = the block's S samples
  * and zeros above.  ws: ffc_dkf_workspace_bytes(plan, B * nblk, H) bytes; finish with ffc_kernel_ifft_grad(plan, ws, B * nblk, H, Lk, ..). */
 int ffc_conv_bwd_dkf_os(const ffc_plan* plan, const void* dout, const void* u, void* ws, int64_t B, int64_t H, int64_t L, void* stream);
+/* The gated form of the two calls above, on kernels of their own: y = postgate * conv_os(u * pregate) + addend and, from the same
+ * launch, out2 = conv_os(u * pregate) * gate2.  pregate, postgate, addend, gate2 / out2 are nullable, contiguous (B, H, L) of the plan
+ * dtype, read at the sample's own index (a wrapped window reads the gate of the previous block with its samples); products and the sum
+ * in fp32, one rounding each.  out2 needs gate2.  One kernel serves the forward (wrap = 1), the input gradient (wrap = 0, conj_kf = 1,
+ * u = dy, pregate = the forward's postgate, postgate = the forward's pregate: y = dx, and gate2 = x: out2 = dpregate) and
+ * dpostgate (the forward again with dy as postgate and no addend).  y and out2 must not overlap each other or any input: the call
+ * returns an error without launching.  16-byte accesses when L % 8 == 0 and every tensor is 16-byte aligned.  Limits as ffc_conv_fwd_os. */
+int ffc_conv_fwd_os_gated(const ffc_plan* plan, const void* u, const void* kf, const void* pregate, const void* postgate,
+                          const void* addend, void* y, const void* gate2, void* out2, int64_t B, int64_t H, int64_t L, int conj_kf,
+                          int wrap, void* stream);
+/* dk_f partial sums of the gated form: window of u * pregate as the forward takes it, window of dout * postgate.  ws and the finishing
+ * call as ffc_conv_bwd_dkf_os. */
+int ffc_conv_bwd_dkf_os_gated(const ffc_plan* plan, const void* dout, const void* u, const void* pregate, const void* postgate,
+                              void* ws, int64_t B, int64_t H, int64_t L, void* stream);
 /* Fused backward (one launch): du = pregate * corr(dout*postgate, k), dpre = u * corr(...) (nullable) and the
  * dk_f partial sums in ws.  Covers monarch_conv_backward{,_r2r,_16_16_16,...} (monarch.cpp:27-32): three
  * transforms per pair like the reference's bwd kernels, dk_f kept in fp32. */
