@@ -102,6 +102,19 @@ struct OsGate {
   void* out2;
   int64_t sbg2, sbo2;
 };
+// History form of the gated blocked rows (ffc_conv_fwd_os_hist / ffc_conv_bwd_dkf_os_hist; kernels of their own again).  A call may start
+// in the middle of a signal: `hist` (B, H, S) holds the S samples of the window's input that precede sample 0 of every row, oldest first
+// and already gated, batch stride sbh, row length S.
+//   in   a wrapped window of block 0 reads its history half, window positions n >= S, from hist[b, h, n - S] (no pregate) instead of zeros;
+//        a null hist keeps the zeros
+//   out  with dhist, the launch runs nblk + 1 blocks per row (OsRows::nblk counts them) and block j of the batch is block j - 1 of the
+//        row: block -1 is the natural-order window at [-S, S), dead below 0, and its S outputs go to dhist[b, h, 0 .. S) as they are
+//        (no gate, no addend, no second output): the gradient of the carried state from the input-gradient launch
+struct OsHist {
+  const void* hist;
+  void* dhist;
+  int64_t sbh;
+};
 
 // One pass of a multi-pass size (fft size N = R * M, M = GEO::N = N1 * Mi; HostPlan::R).  With n = n0 M + n1 Mi + mi and
 // f = k0 + R f', pass k0 computes the M-point circular convolution of
@@ -968,13 +981,13 @@ struct Body {
   // history, the ragged last block ends early, an odd batch has no second plane.  Inside a live chunk every index is >= 0; only `< L`
   // is left per lane.  The integer division of the batch index runs once per plane and copy.
   struct OsPlane { int64_t ro; int s0; bool ok; };      // tensor row (elements), first sample of the block, plane exists
-  static FFC_FN OsPlane os_plane(const ConvArgs& a, const OsRows& o, int64_t sb, int h, int pq, int pl) {
+  static FFC_FN OsPlane os_plane(const ConvArgs& a, const OsRows& o, int64_t sb, int h, int pq, int pl, int shift = 0) {
     const int bi = 2 * pq + pl;
     OsPlane P;
     P.ok = bi < a.B;
     const int b = P.ok ? bi / o.nblk : 0, j = P.ok ? bi - b * o.nblk : 0;
     P.ro = (int64_t)b * sb + (int64_t)h * o.L;
-    P.s0 = j * o.S;
+    P.s0 = (j - shift) * o.S;      // (shift = 1: the history form's block -1, struct OsHist)
     return P;
   }
   static FFC_FN int os_s0(const OsRows& o, const OsPlane& P, int i, bool in) { return P.s0 - ((in && o.wrap && i >= NCH / 2) ? GEO::N : 0); }
@@ -1093,14 +1106,29 @@ struct Body {
   }
   // window of u * pregate -> E.  The loads of GB chunks (both planes, sample and gate) are issued together ahead of the work on them, as
   // rows_store_g does; GB is the caller's register budget (forward 4, dk_f kernel 2).  Zeroing outside [0, L) stays at the LDS write.
-  template <int NC, int GB>
-  static FFC_FN void rows_in_os_g(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un) {
+  // HS (struct OsHist): the history chunks (i >= NCH / 2 of a wrapped window) of a plane that holds block 0 of its row take their base
+  // pointer, s0 = -S and row limit S from `oh.hist` -- a wave-uniform choice per chunk and plane, as os_s0 / os_dead are.  Every lane of
+  // such a chunk is inside the history row, so it is read on the 16-byte arm whatever a.fast says, takes no gate and is never zeroed.
+  template <int NC, int GB, bool HS = false>
+  static FFC_FN void rows_in_os_g(const ConvArgs& a, const OsRows& o, int h, int pq, Unit un, OsHist oh = OsHist()) {
     static_assert(GEO::OUTER && NC % GB == 0, "blocked rows: sizes with an outer digit; whole gate batches");
     const i32 lane = B::opaque(B::lane());
     const int fast = a.fast ? (a.stream ? 2 : 1) : 0;
     const bool hasg = a.pregate != nullptr;
-    const OsPlane P[2] = {os_plane(a, o, a.sbu, h, pq, 0), os_plane(a, o, a.sbu, h, pq, 1)};
-    const OsPlane PG[2] = {os_plane(a, o, a.sbg, h, pq, 0), os_plane(a, o, a.sbg, h, pq, 1)};
+    const int sh = (HS && oh.dhist) ? 1 : 0;
+    const OsPlane P[2] = {os_plane(a, o, a.sbu, h, pq, 0, sh), os_plane(a, o, a.sbu, h, pq, 1, sh)};
+    const OsPlane PG[2] = {os_plane(a, o, a.sbg, h, pq, 0, sh), os_plane(a, o, a.sbg, h, pq, 1, sh)};
+    OsPlane PH[2];
+    bool hp[2] = {false, false};      // the plane's history half comes from oh.hist
+    if constexpr (HS) {
+      OsRows os = o;
+      os.L = o.S;
+#pragma unroll
+      for (int pl = 0; pl < 2; pl++) {
+        PH[pl] = os_plane(a, os, oh.sbh, h, pq, pl, sh);
+        hp[pl] = oh.hist && o.wrap && P[pl].ok && P[pl].s0 == 0;
+      }
+    }
 #pragma unroll
     for (int ib = 0; ib < NC; ib += GB) {
       U4 X[GB][2], G[GB][2];
@@ -1114,6 +1142,10 @@ struct Body {
         for (int pl = 0; pl < 2; pl++) {
           const int s0 = os_s0(o, P[pl], i, true);
           const bool dead = os_dead(o, P[pl], i, s0);
+          if (HS && i >= NCH / 2 && hp[pl]) {
+            X[jj][pl] = os_load8((const uint16_t*)oh.hist + PH[pl].ro, n, -o.S, r0, false, o.S, 1);
+            continue;
+          }
           X[jj][pl] = os_load8((const uint16_t*)a.u + P[pl].ro, n, s0, r0, dead, o.L, fast);
           if (hasg) G[jj][pl] = os_load8((const uint16_t*)a.pregate + PG[pl].ro, n, s0, r0, dead, o.L, fast);
         }
@@ -1131,8 +1163,9 @@ struct Body {
           const int s0 = os_s0(o, P[pl], i, true);
           pred ok = ((row * GEO::Mi + m + s0) < o.L) && !os_dead(o, P[pl], i, s0);
           U4 v = X[jj][pl];
-          if (hasg) v = mul4(v, G[jj][pl]);
-          v = mask4(v, ok);
+          const bool hc = HS && i >= NCH / 2 && hp[pl];
+          if (hasg && !hc) v = mul4(v, G[jj][pl]);
+          if (!hc) v = mask4(v, ok);
           U4 w;
           w.x = B::sel(sw, v.z, v.x); w.y = B::sel(sw, v.w, v.y);
           w.z = B::sel(sw, v.x, v.z); w.w = B::sel(sw, v.y, v.w);
@@ -1143,17 +1176,25 @@ struct Body {
   }
   // window positions n < S of E -> y = raw * postgate + addend, and out2 = raw * gate2, at samples j S + n < L.  The loads of a batch of
   // chunks first, as rows_out_g; a plane that does not exist (odd batch) reads from the start of row (0, h) and stores nothing.
-  template <int GB>
-  static FFC_FN void rows_out_os_g(const ConvArgs& a, const OsRows& o, const OsGate& g, int h, int pq, Unit un) {
+  // HS (struct OsHist, oh.dhist set): a plane that holds block -1 of its row (s0 = -S) loads no operand -- its chunks count as dead, so
+  // the 16-byte arm reads the start of the tensor row -- and stores its S raw samples to oh.dhist on the 16-byte arm, row limit S.
+  template <int GB, bool HS = false>
+  static FFC_FN void rows_out_os_g(const ConvArgs& a, const OsRows& o, const OsGate& g, int h, int pq, Unit un, OsHist oh = OsHist()) {
     static_assert((NCH / 2) % GB == 0, "whole gate batches");
     const i32 lane = B::opaque(B::lane());
     const int fast = a.fast ? (a.stream ? 2 : 1) : 0;
     const bool hasg = a.postgate != nullptr, hasr = a.addend != nullptr, has2 = g.out2 != nullptr;
-    OsPlane PY[2], PG[2], PR[2], P2[2], PO[2];
+    const int sh = (HS && oh.dhist) ? 1 : 0;
+    OsPlane PY[2], PG[2], PR[2], P2[2], PO[2], PH[2];
 #pragma unroll
     for (int pl = 0; pl < 2; pl++) {
-      PY[pl] = os_plane(a, o, a.sby, h, pq, pl); PG[pl] = os_plane(a, o, a.sbp, h, pq, pl); PR[pl] = os_plane(a, o, a.sba, h, pq, pl);
-      P2[pl] = os_plane(a, o, g.sbg2, h, pq, pl); PO[pl] = os_plane(a, o, g.sbo2, h, pq, pl);
+      PY[pl] = os_plane(a, o, a.sby, h, pq, pl, sh); PG[pl] = os_plane(a, o, a.sbp, h, pq, pl, sh); PR[pl] = os_plane(a, o, a.sba, h, pq, pl, sh);
+      P2[pl] = os_plane(a, o, g.sbg2, h, pq, pl, sh); PO[pl] = os_plane(a, o, g.sbo2, h, pq, pl, sh);
+      if constexpr (HS) {
+        OsRows os = o;
+        os.L = o.S;
+        PH[pl] = os_plane(a, os, oh.sbh, h, pq, pl, sh);
+      }
     }
 #pragma unroll
     for (int ib = 0; ib < NCH / 2; ib += GB) {
@@ -1168,7 +1209,7 @@ struct Body {
         for (int pl = 0; pl < 2; pl++) {
           // (the block's start j S lies inside the row, so only its ragged end is clamped or predicated away)
           const int s0 = PY[pl].s0;
-          const bool dead = !PY[pl].ok || s0 + r0 >= o.L;
+          const bool dead = !PY[pl].ok || s0 + r0 >= o.L || (HS && s0 < 0);
           if (hasg) G[jj][pl] = os_load8((const uint16_t*)a.postgate + PG[pl].ro, n, s0, r0, dead, o.L, fast);
           if (hasr) Rr[jj][pl] = os_load8((const uint16_t*)a.addend + PR[pl].ro, n, s0, r0, dead, o.L, fast);
           if (has2) G2[jj][pl] = os_load8((const uint16_t*)g.gate2 + P2[pl].ro, n, s0, r0, dead, o.L, fast);
@@ -1189,6 +1230,10 @@ struct Body {
           v.x = B::sel(sw, w.z, w.x); v.y = B::sel(sw, w.w, w.y);
           v.z = B::sel(sw, w.x, w.z); v.w = B::sel(sw, w.y, w.w);
           const i32 n = row * GEO::Mi + m + PY[pl].s0;
+          if (HS && PY[pl].s0 < 0) {
+            gstore8((uint16_t*)oh.dhist + PH[pl].ro, row * GEO::Mi + m, o.S, 1, PY[pl].ok, v);
+            continue;
+          }
           if (has2) gstore8((uint16_t*)g.out2 + PO[pl].ro, n, o.L, fast, PY[pl].ok, mul4(v, G2[jj][pl]));
           if (hasg && hasr) v = fma4(v, G[jj][pl], Rr[jj][pl]);
           else if (hasg) v = mul4(v, G[jj][pl]);
@@ -2707,10 +2752,12 @@ struct Body {
   // PL: the input rows are plain too (ffc::plain_rows_ok): rows_load_pl / rows_store_pl, no gate, side-product or element-wise arm
   // OS: blocked rows (struct OsRows `o`): the whole window comes in (rows_load_os / rows_store_os, full-height phase A) and only the
   //     window positions n < S go out, so phase C runs its half-height form and rows_out_os moves half of the rows
-  // OSG: the gated form of OS (struct OsGate `og`): rows_in_os_g / rows_out_os_g, a kernel of its own
+  // OSG: 1: the gated form of OS (struct OsGate `og`): rows_in_os_g / rows_out_os_g, a kernel of its own; 2: its history form (struct
+  //      OsHist `oh`), one more kernel
   template <bool HALF, bool PROF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false,
-            bool OSG = false>
-  static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0, OsRows o = OsRows(), OsGate og = OsGate()) {
+            int OSG = 0>
+  static FFC_FN void outer_jobs(const ConvArgs& a, int h, int p0, int p1, int u, Unit un, int wg_linear = 0, OsRows o = OsRows(), OsGate og = OsGate(),
+                                OsHist oh = OsHist()) {
     static_assert(!OSG || OS, "gated blocked rows: a form of the blocked-row kernel");
     static_assert(!GS || (HALF && !RP && !SP && HALF_C), "direct-store phase C: single-pass fft 32768, L <= N/2");
     static_assert(!PL || GS, "plain input rows: a form of the direct-store kernels");
@@ -2778,7 +2825,7 @@ struct Body {
           rows_in_rp<NC>(a, h, p, un, ps);
         } else if constexpr (!ROT) {
           if constexpr (OSG) {
-            rows_in_os_g<NC, 4>(a, o, h, p, un);
+            rows_in_os_g<NC, 4, OSG == 2>(a, o, h, p, un, oh);
           } else if constexpr (OS) {
             rows_load_os<NC>(a, o, h, p, un, X);
             rows_store_os<NC>(a, o, h, p, un, X);
@@ -2880,7 +2927,7 @@ struct Body {
             else rows_out<NC, false>(ar, h, p, un);
           }
         }
-        if constexpr (OSG) rows_out_os_g<4>(a, o, og, h, p, un);
+        if constexpr (OSG) rows_out_os_g<4, OSG == 2>(a, o, og, h, p, un, oh);
         else if constexpr (OS) rows_out_os(a, o, h, p, un);
         else if constexpr (RP) rows_out_rp<NC>(a, h, p, un, ps);
         else rows_out<NC>(a, h, p, un);
@@ -2906,8 +2953,8 @@ struct Body {
     conv_job<HALF, false, SZ, SP, GS, PL>(a, h, chunk);
   }
   // one (head, chunk) job; the tables are already in LDS.  RP: all passes of a multi-pass size
-  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false, bool OSG = false>
-  static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk, OsRows o = OsRows(), OsGate og = OsGate()) {
+  template <bool HALF = false, bool RP = false, bool SZ = false, bool SP = false, bool GS = false, bool PL = false, bool OS = false, int OSG = 0>
+  static FFC_FN void conv_job(const ConvArgs& a, int h, int chunk, OsRows o = OsRows(), OsGate og = OsGate(), OsHist oh = OsHist()) {
     const int wv = B::wave();
     Unit un;
     un.wq = wv % GEO::NW;
@@ -2917,7 +2964,7 @@ struct Body {
     int p1 = p0 + a.ppc;
     if (p1 > a.npair) p1 = a.npair;
     if constexpr (GEO::OUTER) {
-      outer_jobs<HALF, false, RP, SZ, SP, GS, PL, OS, OSG>(a, h, p0, p1, u, un, 0, o, og);
+      outer_jobs<HALF, false, RP, SZ, SP, GS, PL, OS, OSG>(a, h, p0, p1, u, un, 0, o, og, oh);
     } else {
       // one tile of G pairs per wave
       const int q0 = p0 / GEO::G, q1 = (p1 + GEO::G - 1) / GEO::G;

@@ -987,8 +987,9 @@ struct Modes : Body<B, GEO, DT> {
   // that dkf_kernel keeps its code and registers: a change to one loop belongs in the other.
   // G (ffc_conv_bwd_dkf_os_gated, a kernel of its own): the wrapped window is of u * pregate, the S-sample window of dout * postgate
   // (Body::rows_in_os_g, two chunks of loads in flight: the 128-register budget).
-  template <bool G = false>
-  static FFC_FN void dkf_os(const DkfArgs& d, const OsRows& o, int h, int chunk, int wg_linear) {
+  // G = 2 (ffc_conv_bwd_dkf_os_hist, one more kernel): the wrapped window of block 0 takes its history half from `oh.hist` (struct OsHist).
+  template <int G = 0>
+  static FFC_FN void dkf_os(const DkfArgs& d, const OsRows& o, int h, int chunk, int wg_linear, OsHist oh = OsHist()) {
     static_assert(GEO::OUTER, "blocked rows: sizes with an outer digit");
     const ConvArgs& a = d.c;
     BD::setup_tables(a.tab, a.t);
@@ -1016,7 +1017,7 @@ struct Modes : Body<B, GEO, DT> {
       const int p = p0 + it * GEO::UPW + u;
       const bool act = p < p1;
       if (act) {
-        if constexpr (G) BD::template rows_in_os_g<BD::NCH, 2>(a, o, h, p, un);
+        if constexpr (G) BD::template rows_in_os_g<BD::NCH, 2, G == 2>(a, o, h, p, un, oh);
         else BD::template rows_in_os<BD::NCH>(a, o, h, p, un);
         B::lds_fence();
         BD::template outer_stage<true, false>(a.L, un, a.s_fwd);

@@ -229,6 +229,47 @@ inline int os_fast(int64_t L, const void* const* ptrs, int n) {
   return (L % 8 == 0) && !(all & 15);
 }
 
+// ---- history form of the gated blocked rows (struct OsHist; conv_os_h_kernel and dkf_os_h_kernel): os_gated_route's grid and LDS.  The
+// history feeds the wrapped window only, the state gradient comes from the natural-order window only (block -1 has no history half), and
+// both tensors are always accessed 16 bytes at a time, whatever L is.
+static constexpr const char* NO_OS_HIST =
+    "overlap-save history form: fft 4096 / 8192 / 16384 / 32768, a history with wrap = 1 only, a state gradient with wrap = 0 only, both 16-byte aligned";
+template <class GEO>
+inline OsRoute os_hist_route(const ConvArgs& a, const OsRows& o, const OsGate& g, const OsHist& oh) {
+  OsRoute r = os_gated_route<GEO>(a, o, g);
+  if (r.err) return r;
+  if ((oh.hist && !o.wrap) || (oh.dhist && o.wrap) || (((uintptr_t)oh.hist | (uintptr_t)oh.dhist) & 15) || oh.sbh % 8) r.err = NO_OS_HIST;
+  return r;
+}
+// os_limits with the block -1 of every row counted and the (B, H, S) history tensors indexed in 32 bits
+inline const char* os_hist_limits(int64_t N, int64_t B, int64_t H, int64_t L) {
+  if (const char* e = os_limits(N, B, H, L)) return e;
+  if (B * (os_blocks(N, L) + 1) >= ((int64_t)1 << 30) || B * H * (N / 2) >= ((int64_t)1 << 31))
+    return "overlap-save history form: B * (blocks + 1) must be below 2^30, B * H * S below 2^31";
+  return nullptr;
+}
+// os_alias with the history tensors (`helems` elements each): hist is one more input, dhist one more output
+inline const char* os_hist_alias(const void* const* outs, int nout, const void* const* ins, int nin, int64_t elems, const void* hist,
+                                 const void* dhist, int64_t helems) {
+  if (const char* e = os_alias(outs, nout, ins, nin, elems)) return e;
+  const auto hits = [](const void* p, int64_t pe, const void* q, int64_t qe) {
+    const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+    return p && q && a < b + (uintptr_t)qe * 2 && b < a + (uintptr_t)pe * 2;
+  };
+  bool bad = hits(hist, helems, dhist, helems);
+  for (int i = 0; i < nout; i++) bad = bad || hits(outs[i], elems, hist, helems) || hits(outs[i], elems, dhist, helems);
+  for (int i = 0; i < nin; i++) bad = bad || hits(ins[i], elems, dhist, helems);
+  return bad ? "overlap-save history form: an output overlaps an input or another output of the launch" : nullptr;
+}
+// after set_os_rows: contiguous (B, H, S) history tensors; with a state gradient every row gets its block -1
+inline void set_os_hist(ConvArgs* a, OsRows* o, OsHist* oh, const void* hist, void* dhist, int64_t B, int64_t H) {
+  oh->hist = hist; oh->dhist = dhist; oh->sbh = H * o->S;
+  if (dhist) {
+    o->nblk += 1;
+    a->B = (int)(B * o->nblk); a->npair = (a->B + 1) / 2;
+  }
+}
+
 // ---- frequency-sparse fused backward (bwd_sp_kernel, Modes::bwd_sp) and its dk_f -> dk kernel (dkifft_sp_kernel): refused where the
 // forward's sparse form is (fwd_route: GEO::HAS_SP, single pass, 1 <= rows <= 4, no spectrum buffer); one workgroup per (head, chunk)
 struct BwdSpRoute {

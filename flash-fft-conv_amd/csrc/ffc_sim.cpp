@@ -552,6 +552,30 @@ template <class GEO, int DT> struct DkfOsGRun {
     }
   }
 };
+// conv_os_h_kernel / dkf_os_h_kernel (ffc_k_conv_os_h.hip, ffc_k_dkf_os_h.hip)
+template <class GEO, int DT> struct ConvOsHRun {
+  static int run(const ConvArgs& a, const OsRows& o, const OsGate& g, const OsHist& oh) {
+    if (os_hist_route<GEO>(a, o, g, oh).err) return NO_KERNEL;
+    if constexpr (GEO::OUTER) {
+      return sim_jobs(a.H, a.nchunk, GEO::LDS_BYTES, [&](int h, int c) {
+        Body<SimB, GEO, DT>::setup_tables(a.tab, a.t);
+        Body<SimB, GEO, DT>::template conv_job<false, false, false, false, false, false, true, 2>(a, h, c, o, g, oh);
+      });
+    } else {
+      return NO_KERNEL;
+    }
+  }
+};
+template <class GEO, int DT> struct DkfOsHRun {
+  static int run(const DkfArgs& d, const OsRows& o, const OsHist& oh) {
+    if (os_hist_route<GEO>(d.c, o, OsGate(), oh).err) return NO_KERNEL;
+    if constexpr (GEO::OUTER) {
+      return sim_jobs(d.c.H, d.c.nchunk, GEO::LDS_BYTES, [&](int h, int c) { Modes<SimBO, GEO, DT>::template dkf_os<2>(d, o, h, c, h * d.c.nchunk + c, oh); });
+    } else {
+      return NO_KERNEL;
+    }
+  }
+};
 template <class GEO, int DT> struct DkfRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, true>(d); } };
 template <class GEO, int DT> struct BwdRun { static int run(const DkfArgs& d) { return sim_bwd_t<GEO, DT, false>(d); } };
 template <class GEO, int DT> struct DkRun {
@@ -1090,6 +1114,51 @@ int ffcsim_conv_bwd_dkf_os_gated(int N, int dtype, const void* dout, const void*
   std::vector<uint8_t> zs((size_t)H * ffcsim_upw(N) * N * 4 + 16);
   d.zscratch = zs.data();
   int rc = dispatch<DkfOsGRun>(N, dtype, d, o);
+  return rc < 0 ? rc : a.nchunk;
+}
+// The history form (ffc_conv_fwd_os_hist / ffc_conv_bwd_dkf_os_hist), same rules (os_hist_route, os_hist_limits, os_hist_alias, set_os_hist)
+int ffcsim_conv_fwd_os_hist(int N, int dtype, const void* u, const void* kf, const void* pregate, const void* postgate, const void* addend,
+                            void* y, const void* gate2, void* out2, const void* hist, void* dhist, int B, int H, int L, int conj_kf, int wrap) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (B <= 0 || H <= 0 || L <= 0 || os_hist_limits(N, B, H, L)) return -2;
+  const void* const outs[] = {y, out2};
+  const void* const ins[] = {u, pregate, postgate, addend, gate2};
+  if (os_hist_alias(outs, 2, ins, 5, (int64_t)B * H * L, hist, dhist, (int64_t)B * H * (N / 2))) return -3;
+  ConvArgs a{};
+  OsRows o{};
+  OsGate g{};
+  OsHist oh{};
+  a.u = u; a.y = y; a.kf = kf; a.pregate = pregate; a.postgate = postgate; a.tab = p.blob.data(); a.t = p.tabs;
+  set_os_rows(&a, &o, N, B, H, L, wrap ? 1 : 0);
+  set_os_gate(&a, &g, addend, gate2, out2, H, L);
+  set_os_hist(&a, &o, &oh, hist, dhist, B, H);
+  a.nchunk = 1; a.ppc = a.npair; a.conj_kf = conj_kf; a.s_inv = (float)p.s_inv; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R;
+  a.flags = g_sim_flags;
+  return dispatch<ConvOsHRun>(N, dtype, a, o, g, oh);
+}
+int ffcsim_conv_bwd_dkf_os_hist(int N, int dtype, const void* dout, const void* u, const void* pregate, const void* postgate, const void* hist,
+                                float* ws, int B, int H, int L) {
+  HostPlan p;
+  if (!build_plan(N, dtype, &p)) return -1;
+  if (B <= 0 || H <= 0 || L <= 0 || os_hist_limits(N, B, H, L)) return -2;
+  DkfArgs d{};
+  OsRows o{};
+  OsHist oh{};
+  ConvArgs& a = d.c;
+  a.u = u; a.pregate = pregate; a.postgate = postgate; a.tab = p.blob.data(); a.t = p.tabs;
+  set_os_rows(&a, &o, N, B, H, L, 1);
+  set_os_hist(&a, &o, &oh, hist, nullptr, B, H);
+  d.sbd = d.sbdu = d.sbdpre = d.sbdpost = (int64_t)H * L;
+  a.nchunk = 1; a.ppc = a.npair; a.s_fwd = (float)p.s_fwd;
+  a.fast = (L % 8 == 0) && !g_force_slow;
+  a.R = p.R;
+  d.dout = dout; d.ws = ws;
+  std::vector<uint8_t> zs((size_t)H * ffcsim_upw(N) * N * 4 + 16);
+  d.zscratch = zs.data();
+  int rc = dispatch<DkfOsHRun>(N, dtype, d, o, oh);
   return rc < 0 ? rc : a.nchunk;
 }
 

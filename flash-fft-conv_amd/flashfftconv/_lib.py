@@ -49,6 +49,8 @@ def lib():
         L.ffc_conv_bwd_dkf_os.argtypes = [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_fwd_os_gated.argtypes = [c_vp] * 9 + [c_i64, c_i64, c_i64, c_int, c_int, c_vp]
         L.ffc_conv_bwd_dkf_os_gated.argtypes = [c_vp] * 6 + [c_i64, c_i64, c_i64, c_vp]
+        L.ffc_conv_fwd_os_hist.argtypes = [c_vp] * 11 + [c_i64, c_i64, c_i64, c_int, c_int, c_vp]
+        L.ffc_conv_bwd_dkf_os_hist.argtypes = [c_vp] * 7 + [c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd_gated.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd_sparse.argtypes = [c_vp] * 11 + [c_i64, c_i64, c_i64, c_int, c_vp]

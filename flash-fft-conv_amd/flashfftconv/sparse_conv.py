@@ -6,6 +6,7 @@ Same classes, constructor arguments and semantics as the reference's torch.fft d
   PartialFFTConv(N_partial)(x, k)          y = conv(x, k[..., :N_partial]),             fft size 2L
   PartialFFTConv(N_partial, overlap_save=True)   the same y block by block for N_partial <= 16384: any L, blocks of max(2048, nextpow2(taps))
   PartialFFTConv(..)(x, k, pregate, postgate, residual)   y = postgate * conv(x * pregate, k[..., :N_partial]) + residual, each optional
+  PartialFFTConv(.., overlap_save=True)(x, k, .., state=s, return_state=True)   a row in pieces: (y, new state), the filter's history carried over
   FrequencySparseFFTConv(N_partial)(x, k)  y = irfft(rfft(x) * rfft(k) * [f < N_partial // 2]), fft size 2L
 
 x is (B, H, L) bf16/fp16 on the GPU, k is (H, Lk) fp32 (the reference demos up-cast x to fp32 and back;
@@ -160,6 +161,67 @@ class _OverlapSaveGatedFn(torch.autograd.Function):
         return dx if need[0] else None, dk, dpre, dpost, dy if need[4] else None, None
 
 
+def _conv_os_hist(plan, x, kf, conj, wrap, pregate=None, postgate=None, addend=None, gate2=None, hist=None, want_dhist=False):
+    """ffc_conv_fwd_os_hist: _conv_os_gated with the (B, H, S) history of block 0 (wrap) or, with want_dhist, a block -1 per row whose S
+    outputs are the history's gradient -> (y, out2 or None, dhist or None)"""
+    B, H, L = x.shape
+    y = torch.empty_like(x)
+    out2 = None if gate2 is None else torch.empty_like(x)
+    dhist = torch.empty(B, H, plan.seqlen // 2, dtype=x.dtype, device=x.device) if want_dhist else None
+    _lib.check(_lib.lib().ffc_conv_fwd_os_hist(plan.handle, _lib.ptr(x), _lib.ptr(kf), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(addend),
+                                               _lib.ptr(y), _lib.ptr(gate2), _lib.ptr(out2), _lib.ptr(hist), _lib.ptr(dhist), B, H, L, int(conj),
+                                               int(wrap), _lib.stream_ptr()), "ffc_conv_fwd_os_hist")
+    return y, out2, dhist
+
+
+def _dkf_os_hist(plan, dy, x, pregate, postgate, hist):
+    """ffc_conv_bwd_dkf_os_hist: _dkf_os_gated with the history in block 0's window -> (B * nblk, workspace)"""
+    B, H, L = x.shape
+    nb = B * (-(-L // (plan.seqlen // 2)))
+    ws = torch.empty(_C._ws_bytes(plan, nb, H), dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().ffc_conv_bwd_dkf_os_hist(plan.handle, _lib.ptr(dy), _lib.ptr(x), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(hist),
+                                                   _lib.ptr(ws), B, H, L, _lib.stream_ptr()), "ffc_conv_bwd_dkf_os_hist")
+    return nb, ws
+
+
+class _OverlapSaveStateFn(torch.autograd.Function):
+    """_OverlapSaveGatedFn for a call that starts in the middle of a signal: `state` (B, H, S) holds the S samples of x * pregate before
+    the call's first one and is block 0's history in every launch that takes the wrapped window (forward, dpostgate, dk_f).  Its
+    gradient is block -1 of the input-gradient launch, run only where it is asked for; that launch is skipped when neither x, pregate
+    nor the state wants a gradient.  Where only the state wants one, the launch still computes and stores dx of the nblk blocks (the entry
+    point has no form without y) and the result is dropped.  Gates stay optional: without any, the history kernels run with null gates."""
+
+    @staticmethod
+    def forward(ctx, x, k, pregate, postgate, residual, state, plan):
+        with torch.cuda.device(x.device):
+            kf = _C._kernel_fft(plan, k)
+            y, _, _ = _conv_os_hist(plan, x, kf, False, True, pregate, postgate, residual, None, state)
+        ctx.save_for_backward(x, kf, pregate, postgate, state)
+        ctx.plan, ctx.k_shape, ctx.k_dtype = plan, tuple(k.shape), k.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, kf, pregate, postgate, state = ctx.saved_tensors
+        plan, (H, Lk) = ctx.plan, ctx.k_shape
+        need = ctx.needs_input_grad
+        dy = dy.contiguous()
+        dx = dk = dpre = dpost = dstate = None
+        with torch.cuda.device(x.device):
+            want_dpre = need[2] and pregate is not None
+            if need[0] or want_dpre or need[5]:
+                dx, dpre, dstate = _conv_os_hist(plan, dy, kf, True, False, postgate, pregate, None, x if want_dpre else None, None, need[5])
+            if need[3] and postgate is not None:
+                dpost, _, _ = _conv_os_hist(plan, x, kf, False, True, pregate, dy, None, None, state)
+            if need[1]:
+                nb, ws = _dkf_os_hist(plan, dy, x, pregate, postgate, state)
+                dk = torch.empty(H, Lk, dtype=torch.float32, device=x.device)
+                _lib.check(_lib.lib().ffc_kernel_ifft_grad(plan.handle, _lib.ptr(ws), nb, H, Lk, _lib.ptr(dk), _lib.stream_ptr()),
+                           "ffc_kernel_ifft_grad")
+                dk = dk.to(ctx.k_dtype)
+        return dx if need[0] else None, dk, dpre, dpost, dy if need[4] else None, dstate, None
+
+
 def _check_gate(x, name, g):
     if not torch.is_tensor(g):
         raise RuntimeError(f"PartialFFTConv: {name} must be a tensor")
@@ -176,21 +238,35 @@ class PartialFFTConv(_ConvCache):
     S = os_fft_size(P) / 2 samples and each block runs on the one-launch fused kernel of fft size 2 S with the previous block as its
     history (ffc_conv_fwd_os): any sequence length, work per sample set by P and not by L, and nothing kept for the backward beyond x
     and k_f.  Rows that fit one block (L <= S) keep the 2 L route where 2 L is a supported fft size, as do filters of more than 16384
-    taps.  Gates and `residual` are fused into the blocked launches as well (ffc_conv_fwd_os_gated, ffc_conv_bwd_dkf_os_gated): see forward."""
+    taps.  Gates and `residual` are fused into the blocked launches as well (ffc_conv_fwd_os_gated, ffc_conv_bwd_dkf_os_gated): see forward.
+
+    A row may be fed in pieces of any lengths: `state=` carries the last `state_len` = max(2048, nextpow2(N_partial)) samples of
+    x * pregate from one call to the next (ffc_conv_fwd_os_hist, ffc_conv_bwd_dkf_os_hist), and the pieces give what one call on the whole
+    row gives.  Such a call always takes the blocked route, whatever its length."""
 
     def __init__(self, N_partial, overlap_save=False):
         super().__init__(N_partial)
         self.overlap_save = overlap_save
+        # S: length of the carried state, the block length of the route for filters of N_partial taps (None: no overlap-save route)
+        self.state_len = os_fft_size(N_partial) // 2 if overlap_save and 1 <= N_partial <= OS_MAX_TAPS else None
 
-    def _os_plan(self, x, k):
-        """the block plan of the overlap-save route for this call, or None: today's 2 L route"""
+    def _os_plan(self, x, k, stateful=False):
+        """the block plan of the overlap-save route for this call, or None: today's 2 L route.  stateful: a call that takes or returns a
+        state runs blocks of state_len samples whatever L and k's length are, or raises"""
+        if stateful:
+            if self.state_len is None:
+                raise RuntimeError("PartialFFTConv: state= / return_state= need overlap_save=True and N_partial <= 16384")
+            if not torch.is_tensor(x) or not torch.is_tensor(k) or x.dim() != 3 or k.dim() != 2 or x.shape[-1] < 1 or k.shape[-1] < 1:
+                raise RuntimeError("PartialFFTConv: state= / return_state= need x of shape (B, H, L >= 1) and k of shape (H, Lk >= 1)")
+            if x.dtype not in (torch.bfloat16, torch.float16):
+                raise RuntimeError(f"PartialFFTConv: x must be a bf16 / fp16 tensor, got {x.dtype}")
         if not self.overlap_save or not torch.is_tensor(x) or not torch.is_tensor(k) or x.dim() != 3 or k.dim() != 2:
             return None
         L, taps = x.shape[-1], min(self.N_partial, k.shape[-1])
         if x.dtype not in (torch.bfloat16, torch.float16) or L < 1 or not 1 <= taps <= OS_MAX_TAPS:
             return None
-        n = os_fft_size(taps)
-        if L <= n // 2 and 2 * L in _C.SUPPORTED_SEQLENS:
+        n = 2 * self.state_len if stateful else os_fft_size(taps)
+        if not stateful and L <= n // 2 and 2 * L in _C.SUPPORTED_SEQLENS:
             return None
         if x.numel() >= 2 ** 31 or L + n >= 2 ** 31:      # (the kernels index a row in 32 bits up to one window past its end)
             raise RuntimeError("PartialFFTConv: B * H * L and L + the block fft size must be below 2^31")
@@ -202,11 +278,27 @@ class PartialFFTConv(_ConvCache):
             raise RuntimeError(f"PartialFFTConv: k has {k.shape[0]} rows, x {x.shape[1]} heads")
         return _C.get_plan(n, x.dtype, x.device)
 
-    def forward(self, x, k, pregate=None, postgate=None, residual=None):
+    def _check_state(self, x, state):
+        if not torch.is_tensor(state):
+            raise RuntimeError("PartialFFTConv: state must be a tensor")
+        if state.device != x.device:
+            raise RuntimeError(f"PartialFFTConv: state is on {state.device}, x on {x.device}")
+        if tuple(state.shape) != (x.shape[0], x.shape[1], self.state_len) or state.dtype != x.dtype:
+            raise RuntimeError(f"PartialFFTConv: state must be {(x.shape[0], x.shape[1], self.state_len)} {x.dtype}, got {tuple(state.shape)} {state.dtype}")
+        if not state.is_contiguous():
+            raise RuntimeError("PartialFFTConv: state must be contiguous")
+
+    def forward(self, x, k, pregate=None, postgate=None, residual=None, state=None, return_state=False):
         """y = postgate * conv(x * pregate, k[..., :N_partial]) + residual; each of pregate, postgate, residual (x's shape, dtype and device)
         is optional on its own.  Differentiable in x, k and the gates; residual receives the incoming gradient.  On the blocked route a
         call with a gate or a residual keeps x, the gates and k_f for the backward (no spectra, no output before the gate) and recomputes
-        the forward once where dpostgate is asked for; a call with neither keeps x and k_f."""
+        the forward once where dpostgate is asked for; a call with neither keeps x and k_f.
+
+        state (B, H, state_len), x's dtype and device, contiguous; None: zeros): the samples of x * pregate that precede this call's,
+        oldest first, already gated.  return_state=True returns (y, new_state) with new_state = cat(state, x * pregate)[..., -state_len:],
+        the product rounded once to the module dtype as the kernel rounds it.  Differentiable in the state as well."""
+        if state is not None or return_state:
+            return self._forward_state(x, k, pregate, postgate, residual, state, return_state)
         plan = self._os_plan(x, k)
         if plan is None:
             if (pregate is None) != (postgate is None):      # FlashFFTConv takes both gates or none: the missing one is all ones
@@ -222,6 +314,36 @@ class PartialFFTConv(_ConvCache):
             _C._check_residual(x, residual)
         pregate, postgate, residual = (None if t is None else t.contiguous() for t in (pregate, postgate, residual))
         return _OverlapSaveGatedFn.apply(x.contiguous(), k[..., : self.N_partial], pregate, postgate, residual, plan)
+
+    def _forward_state(self, x, k, pregate, postgate, residual, state, return_state):
+        plan = self._os_plan(x, k, stateful=True)
+        for name, g in (("pregate", pregate), ("postgate", postgate)):
+            if g is not None:
+                _check_gate(x, name, g)
+        if residual is not None:
+            _C._check_residual(x, residual)
+        if state is not None:
+            self._check_state(x, state)
+            if state.data_ptr() % 16:      # (the kernels read the history 16 bytes at a time)
+                state = state.clone()
+        x = x.contiguous()
+        pregate, postgate, residual = (None if t is None else t.contiguous() for t in (pregate, postgate, residual))
+        if state is None and pregate is None and postgate is None and residual is None:
+            y = _OverlapSaveFn.apply(x, k[..., : self.N_partial], plan)
+        elif state is None:
+            y = _OverlapSaveGatedFn.apply(x, k[..., : self.N_partial], pregate, postgate, residual, plan)
+        else:
+            y = _OverlapSaveStateFn.apply(x, k[..., : self.N_partial], pregate, postgate, residual, state, plan)
+        if not return_state:
+            return y
+        # The new state is composed in torch from the tails: at most S samples per row are touched, against the L the kernels move, and
+        # as plain torch ops their gradients reach x, pregate and the old state through autograd with no code of ours.
+        S, L = self.state_len, x.shape[-1]
+        tail = x[..., -S:] if pregate is None else x[..., -S:] * pregate[..., -S:]
+        if L < S:
+            old = state[..., L:] if state is not None else x.new_zeros(x.shape[0], x.shape[1], S - L)
+            tail = torch.cat((old, tail), dim=-1)
+        return y, tail.contiguous()
 
 
 class FrequencySparseFFTConv(_ConvCache):

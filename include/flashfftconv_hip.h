@@ -107,6 +107,19 @@ int ffc_conv_fwd_os_gated(const ffc_plan* plan, const void* u, const void* kf, c
  * call as ffc_conv_bwd_dkf_os. */
 int ffc_conv_bwd_dkf_os_gated(const ffc_plan* plan, const void* dout, const void* u, const void* pregate, const void* postgate,
                               void* ws, int64_t B, int64_t H, int64_t L, void* stream);
+/* The history form of the two gated calls, on kernels of their own: a call that starts in the middle of a signal.  hist (nullable:
+ * zeros) is contiguous (B, H, S = N' / 2) of the plan dtype, 16-byte aligned, and holds the S samples of the window's input that precede
+ * sample 0 of every row, oldest first and ALREADY gated: with wrap = 1 the window of block 0 reads its history half from it instead of
+ * zeros and applies no pregate there.  dhist (nullable, same shape; wrap = 0 only): the launch runs one more block per row, block -1
+ * with the natural-order window at [-S, S), and stores that block's S outputs to dhist with no gate product -- with conj_kf = 1 on dy
+ * the gradient of hist.  hist needs wrap = 1.  Neither may overlap another tensor of the launch.  Everything else, gates included, as
+ * ffc_conv_fwd_os_gated; B * (nblk + 1) < 2^30 and B * H * S < 2^31 in addition to its limits. */
+int ffc_conv_fwd_os_hist(const ffc_plan* plan, const void* u, const void* kf, const void* pregate, const void* postgate,
+                         const void* addend, void* y, const void* gate2, void* out2, const void* hist, void* dhist, int64_t B,
+                         int64_t H, int64_t L, int conj_kf, int wrap, void* stream);
+/* dk_f partial sums with the history in block 0's window of u * pregate.  ws and the finishing call as ffc_conv_bwd_dkf_os. */
+int ffc_conv_bwd_dkf_os_hist(const ffc_plan* plan, const void* dout, const void* u, const void* pregate, const void* postgate,
+                             const void* hist, void* ws, int64_t B, int64_t H, int64_t L, void* stream);
 /* Fused backward (one launch): du = pregate * corr(dout*postgate, k), dpre = u * corr(...) (nullable) and the
  * dk_f partial sums in ws.  Covers monarch_conv_backward{,_r2r,_16_16_16,...} (monarch.cpp:27-32): three
  * transforms per pair like the reference's bwd kernels, dk_f kept in fp32. */
