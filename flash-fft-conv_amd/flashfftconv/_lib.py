@@ -51,6 +51,10 @@ def lib():
         L.ffc_conv_bwd_dkf_os_gated.argtypes = [c_vp] * 6 + [c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_fwd_os_hist.argtypes = [c_vp] * 11 + [c_i64, c_i64, c_i64, c_int, c_int, c_vp]
         L.ffc_conv_bwd_dkf_os_hist.argtypes = [c_vp] * 7 + [c_i64, c_i64, c_i64, c_vp]
+        L.ffc_partial_step_split.argtypes = [c_i64, c_i64, c_int]; L.ffc_partial_step_split.restype = c_i64
+        L.ffc_partial_step_nsplit.argtypes = [c_i64, c_i64]; L.ffc_partial_step_nsplit.restype = c_i64
+        L.ffc_partial_step_fwd.argtypes = [c_int] + [c_vp] * 9 + [c_i64] * 6 + [c_vp]
+        L.ffc_partial_step_bwd.argtypes = [c_int] + [c_vp] * 13 + [c_i64] * 7 + [c_vp]
         L.ffc_conv_bwd.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd_gated.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp]
         L.ffc_conv_bwd_sparse.argtypes = [c_vp] * 11 + [c_i64, c_i64, c_i64, c_int, c_vp]

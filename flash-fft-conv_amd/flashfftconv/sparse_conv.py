@@ -7,6 +7,7 @@ Same classes, constructor arguments and semantics as the reference's torch.fft d
   PartialFFTConv(N_partial, overlap_save=True)   the same y block by block for N_partial <= 16384: any L, blocks of max(2048, nextpow2(taps))
   PartialFFTConv(..)(x, k, pregate, postgate, residual)   y = postgate * conv(x * pregate, k[..., :N_partial]) + residual, each optional
   PartialFFTConv(.., overlap_save=True)(x, k, .., state=s, return_state=True)   a row in pieces: (y, new state), the filter's history carried over
+  PartialFFTConv(.., overlap_save="direct")   the same, pieces of 1 .. 64 samples on the direct step kernels (generation): no transform, one launch
   FrequencySparseFFTConv(N_partial)(x, k)  y = irfft(rfft(x) * rfft(k) * [f < N_partial // 2]), fft size 2L
 
 x is (B, H, L) bf16/fp16 on the GPU, k is (H, Lk) fp32 (the reference demos up-cast x to fp32 and back;
@@ -222,6 +223,79 @@ class _OverlapSaveStateFn(torch.autograd.Function):
         return dx if need[0] else None, dk, dpre, dpost, dy if need[4] else None, dstate, None
 
 
+STEP_MAX = 64      # overlap_save="direct": a stateful piece of up to this many samples runs the direct step kernels (ffc_partial_step_fwd)
+_DT = {torch.bfloat16: 0, torch.float16: 1}
+
+
+def _step_fwd(x, k, taps, S, pregate=None, postgate=None, residual=None, state=None, want_state=True, want_raw=False, new_state=None):
+    """ffc_partial_step_fwd on a contiguous (B, H, L <= STEP_MAX) piece behind `state` (B, H, S; None: zeros), k (H, Lk) fp32: one launch
+    -> (y, new_state or None, the fp32 sums before the postgate or None)"""
+    B, H, L = x.shape
+    y = torch.empty_like(x)
+    if new_state is None and want_state:
+        new_state = torch.empty(B, H, S, dtype=x.dtype, device=x.device)
+    raw = torch.empty(B, H, L, dtype=torch.float32, device=x.device) if want_raw else None
+    _lib.check(_lib.lib().ffc_partial_step_fwd(_DT[x.dtype], _lib.ptr(x), _lib.ptr(k), _lib.ptr(pregate), _lib.ptr(postgate), _lib.ptr(residual),
+                                               _lib.ptr(state), _lib.ptr(y), _lib.ptr(new_state), _lib.ptr(raw), B, H, L, S, k.shape[-1], taps,
+                                               _lib.stream_ptr()), "ffc_partial_step_fwd")
+    return y, new_state, raw
+
+
+def _step_bwd(dy, x, k, taps, S, pregate, postgate, state, raw, dnew, want_dx, want_dk, want_dpre, want_dpost, want_dstate):
+    """ffc_partial_step_bwd: every gradient that is asked for from one launch -> (dx, dk partial sums (nsplit, H, taps) fp32, dpregate,
+    dpostgate, dstate), None where not asked for"""
+    B, H, L = x.shape
+    dx = torch.empty_like(x) if want_dx else None
+    dpre = torch.empty_like(x) if want_dpre else None
+    dpost = torch.empty_like(x) if want_dpost else None
+    dstate = torch.empty(B, H, S, dtype=x.dtype, device=x.device) if want_dstate else None
+    nsplit = _lib.lib().ffc_partial_step_nsplit(B, H)
+    dkp = torch.empty(nsplit, H, taps, dtype=torch.float32, device=x.device) if want_dk else None
+    _lib.check(_lib.lib().ffc_partial_step_bwd(_DT[x.dtype], _lib.ptr(dy), _lib.ptr(x), _lib.ptr(k), _lib.ptr(pregate), _lib.ptr(postgate),
+                                               _lib.ptr(state), _lib.ptr(raw), _lib.ptr(dnew), _lib.ptr(dx), _lib.ptr(dpre), _lib.ptr(dpost),
+                                               _lib.ptr(dstate), _lib.ptr(dkp), nsplit, B, H, L, S, k.shape[-1], taps, _lib.stream_ptr()),
+               "ffc_partial_step_bwd")
+    return dx, dkp, dpre, dpost, dstate
+
+
+class _DirectStepFn(torch.autograd.Function):
+    """(y, new_state) of one direct step: a single launch each way.  Keeps x, k, the gates, the state and, where dpostgate will be asked
+    for, the fp32 sums before the postgate (L values per row).  The backward takes the gradients of both outputs (the one that arrives
+    on new_state is the shifted part of dstate and dx); the dk partial sums of a split batch are added in order by sum(0)."""
+
+    @staticmethod
+    def forward(ctx, x, k, pregate, postgate, residual, state, taps, S, want_state):
+        kc = k if k.dtype == torch.float32 and k.is_contiguous() else k.float().contiguous()
+        want_raw = postgate is not None and ctx.needs_input_grad[3]
+        with torch.cuda.device(x.device):
+            y, new_state, raw = _step_fwd(x, kc, taps, S, pregate, postgate, residual, state, want_state, want_raw)
+        ctx.save_for_backward(x, kc, pregate, postgate, state, raw)
+        ctx.taps, ctx.S, ctx.k_shape, ctx.k_dtype = taps, S, tuple(k.shape), k.dtype
+        ctx.set_materialize_grads(False)
+        return y, new_state
+
+    @staticmethod
+    def backward(ctx, dy, dnew):
+        x, k, pregate, postgate, state, raw = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dy = torch.zeros_like(x) if dy is None else dy.contiguous()
+        if dnew is not None:
+            dnew = dnew.contiguous()
+            if dnew.data_ptr() % 16:
+                dnew = dnew.clone()
+        want_dpre, want_dpost = need[2] and pregate is not None, need[3] and postgate is not None
+        with torch.cuda.device(x.device):
+            dx, dkp, dpre, dpost, dstate = _step_bwd(dy, x, k, ctx.taps, ctx.S, pregate, postgate, state, raw, dnew, need[0], need[1],
+                                                     want_dpre, want_dpost, need[5] and state is not None)
+        dk = None
+        if need[1]:
+            dk = dkp[0] if dkp.shape[0] == 1 else dkp.sum(0)
+            if ctx.k_shape[1] > ctx.taps:
+                dk = torch.nn.functional.pad(dk, (0, ctx.k_shape[1] - ctx.taps))
+            dk = dk.to(ctx.k_dtype)
+        return dx, dk, dpre, dpost, dy if need[4] else None, dstate, None, None, None
+
+
 def _check_gate(x, name, g):
     if not torch.is_tensor(g):
         raise RuntimeError(f"PartialFFTConv: {name} must be a tensor")
@@ -242,7 +316,13 @@ class PartialFFTConv(_ConvCache):
 
     A row may be fed in pieces of any lengths: `state=` carries the last `state_len` = max(2048, nextpow2(N_partial)) samples of
     x * pregate from one call to the next (ffc_conv_fwd_os_hist, ffc_conv_bwd_dkf_os_hist), and the pieces give what one call on the whole
-    row gives.  Such a call always takes the blocked route, whatever its length."""
+    row gives.  Such a call always takes the blocked route, whatever its length.
+
+    overlap_save="direct": overlap_save=True in everything but one case.  A call with a state (state= or return_state=True) whose piece has
+    at most STEP_MAX = 64 samples runs the direct step kernels instead (ffc_partial_step_fwd / _bwd: taps multiply-adds per sample on
+    k in fp32, no transform of k, the new state written by the same launch).  The states of the two routes are the same tensors, so one
+    module prefills a prompt on the blocked route and then generates sample by sample on the direct one.  The direct route refuses a
+    state that is not 16-byte aligned where the blocked route copies it."""
 
     def __init__(self, N_partial, overlap_save=False):
         super().__init__(N_partial)
@@ -250,9 +330,10 @@ class PartialFFTConv(_ConvCache):
         # S: length of the carried state, the block length of the route for filters of N_partial taps (None: no overlap-save route)
         self.state_len = os_fft_size(N_partial) // 2 if overlap_save and 1 <= N_partial <= OS_MAX_TAPS else None
 
-    def _os_plan(self, x, k, stateful=False):
+    def _os_plan(self, x, k, stateful=False, want_plan=True):
         """the block plan of the overlap-save route for this call, or None: today's 2 L route.  stateful: a call that takes or returns a
-        state runs blocks of state_len samples whatever L and k's length are, or raises"""
+        state runs blocks of state_len samples whatever L and k's length are, or raises.  want_plan=False: the checks alone (a direct
+        step needs no plan) -> True"""
         if stateful:
             if self.state_len is None:
                 raise RuntimeError("PartialFFTConv: state= / return_state= need overlap_save=True and N_partial <= 16384")
@@ -276,7 +357,7 @@ class PartialFFTConv(_ConvCache):
             raise RuntimeError(f"PartialFFTConv: k is on {k.device}, x on {x.device}")
         if k.shape[0] != x.shape[1]:
             raise RuntimeError(f"PartialFFTConv: k has {k.shape[0]} rows, x {x.shape[1]} heads")
-        return _C.get_plan(n, x.dtype, x.device)
+        return _C.get_plan(n, x.dtype, x.device) if want_plan else True
 
     def _check_state(self, x, state):
         if not torch.is_tensor(state):
@@ -316,7 +397,8 @@ class PartialFFTConv(_ConvCache):
         return _OverlapSaveGatedFn.apply(x.contiguous(), k[..., : self.N_partial], pregate, postgate, residual, plan)
 
     def _forward_state(self, x, k, pregate, postgate, residual, state, return_state):
-        plan = self._os_plan(x, k, stateful=True)
+        direct = self.overlap_save == "direct" and torch.is_tensor(x) and x.dim() == 3 and x.shape[-1] <= STEP_MAX
+        plan = self._os_plan(x, k, stateful=True, want_plan=not direct)
         for name, g in (("pregate", pregate), ("postgate", postgate)):
             if g is not None:
                 _check_gate(x, name, g)
@@ -324,10 +406,15 @@ class PartialFFTConv(_ConvCache):
             _C._check_residual(x, residual)
         if state is not None:
             self._check_state(x, state)
-            if state.data_ptr() % 16:      # (the kernels read the history 16 bytes at a time)
+            if state.data_ptr() % 16 and not direct:      # (the kernels read the history 16 bytes at a time; the step entry point refuses)
                 state = state.clone()
         x = x.contiguous()
         pregate, postgate, residual = (None if t is None else t.contiguous() for t in (pregate, postgate, residual))
+        if direct:
+            # one launch: y, the new state and (for dpostgate) the sums before the gate; states are those of the blocked route
+            y, new_state = _DirectStepFn.apply(x, k, pregate, postgate, residual, state, min(self.N_partial, k.shape[-1]), self.state_len,
+                                               return_state)
+            return (y, new_state) if return_state else y
         if state is None and pregate is None and postgate is None and residual is None:
             y = _OverlapSaveFn.apply(x, k[..., : self.N_partial], plan)
         elif state is None:

@@ -120,6 +120,29 @@ int ffc_conv_fwd_os_hist(const ffc_plan* plan, const void* u, const void* kf, co
 /* dk_f partial sums with the history in block 0's window of u * pregate.  ws and the finishing call as ffc_conv_bwd_dkf_os. */
 int ffc_conv_bwd_dkf_os_hist(const ffc_plan* plan, const void* dout, const void* u, const void* pregate, const void* postgate,
                              const void* hist, void* ws, int64_t B, int64_t H, int64_t L, void* stream);
+/* Direct step of the partial convolution: a piece of 1 <= L <= 64 new samples per row behind a carried state, with no transform and no
+ * plan (dtype: FFC_DT_*).  w = cat(state, x * pregate) per row, the product rounded once to dtype;
+ *   y[b,h,t] = postgate[b,h,t] * sum_{j < taps} k[h,j] * w[b,h,S+t-j] + residual[b,h,t]     (fp32 sums, one rounding at the store)
+ *   new_state = w[..., L : L + S]                                                              (bit-exact)
+ * x, the gates, residual, y are contiguous (B, H, L); state (nullable: zeros) and new_state (nullable: not written) contiguous (B, H, S),
+ * 16-byte aligned and not overlapping; k (H, Lk) fp32 with taps <= Lk; raw (nullable) receives the sums before the gate as fp32
+ * (B, H, L), which ffc_partial_step_bwd needs for dpostgate.  S a power of two, 2048 <= S <= 16384, taps <= S, B * H * S < 2^31.  Any
+ * violation returns an error before anything is launched.  One workgroup per head and batch slice:
+ * ffc_partial_step_split(B, H, num_cu) is the number of slices (grid = H * slices; a slice has ceil(B / n) rows, n the largest count
+ * <= ceil(2 num_cu / H) that leaves every slice at least 4 rows), ffc_partial_step_nsplit the same on the current device. */
+int64_t ffc_partial_step_split(int64_t B, int64_t H, int num_cu);
+int64_t ffc_partial_step_nsplit(int64_t B, int64_t H);
+int ffc_partial_step_fwd(int dtype, const void* x, const float* k, const void* pregate, const void* postgate, const void* residual,
+                         const void* state, void* y, void* new_state, float* raw, int64_t B, int64_t H, int64_t L, int64_t S, int64_t Lk,
+                         int64_t taps, void* stream);
+/* Its backward in one launch, every output nullable and skipped: with g = dy * postgate and dw[i] = sum_t g[t] k[S+t-i] +
+ * dstate_new[i-L] (dstate_new nullable: zeros; the gradient that arrived on new_state), dstate = dw[:S], dxg = dw[S:], dx = dxg * pregate,
+ * dpregate = dxg * x, dpostgate = dy * raw, and dk_part (nsplit, H, taps) fp32 with dk[h,j] = sum over the slices of
+ * sum_b sum_t g[b,t] w[b,S+t-j] (no atomics: the caller adds the nsplit = ffc_partial_step_nsplit(B, H) slices in order). */
+int ffc_partial_step_bwd(int dtype, const void* dy, const void* x, const float* k, const void* pregate, const void* postgate,
+                         const void* state, const float* raw, const void* dstate_new, void* dx, void* dpregate, void* dpostgate,
+                         void* dstate, float* dk_part, int64_t nsplit, int64_t B, int64_t H, int64_t L, int64_t S, int64_t Lk, int64_t taps,
+                         void* stream);
 /* Fused backward (one launch): du = pregate * corr(dout*postgate, k), dpre = u * corr(...) (nullable) and the
  * dk_f partial sums in ws.  Covers monarch_conv_backward{,_r2r,_16_16_16,...} (monarch.cpp:27-32): three
  * transforms per pair like the reference's bwd kernels, dk_f kept in fp32. */
